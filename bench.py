@@ -11,9 +11,12 @@ forward with 7 EPA fusions, CFG merge, two DDIM updates.  Workload = BASELINE.js
 (CFG pair => 40 view samples + 2 pano samples per step), SD-2-base UNet shapes, synthetic seeded
 weights and inputs (no checkpoint / dataset is reachable offline).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with device events around every launch
-of the dominant kernel family in an extra instrumented step after the timed region; `cpu_baseline`
-times the CPU oracle (oracle/, test infrastructure) on a bounded sample on the host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints it
+(`value` steps/s, `ms_per_step`); --dump-outputs DIR also writes the latents the last timed step
+left as DIR/<name>.npy.  The extras run only with --full: `roofline` is measured live with device
+events around every launch of the dominant kernel family in an extra instrumented step after the
+timed region; `cpu_baseline` times the CPU oracle (oracle/, test infrastructure) on a bounded sample
+on the host cores; `training_step` times the training step through the same boundary.
 """
 import argparse
 import json
@@ -278,124 +281,11 @@ def usable_cores():
     return max(1, min(n, 64))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"],
-                    help="16-bit MFMA operand type.  fp16 (default) runs the MIXED scheme -- fp32 residual streams + "
-                         "split-precision stream-path GEMMs -- the configuration that meets north_star's 1e-3 parity bar "
-                         "(tests/test_gpu_mixed.py); bf16 runs the all-16-bit scheme of round 1 (1.2e-2), a labelled secondary line")
-    ap.add_argument("--precision", default=None, choices=["mixed", "fast"], help="override the scheme of --dtype")
-    ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-training-leg", action="store_true",
-                    help="skip the extra `training_step` measurement (N = 1 only; --no-cpu-baseline skips it too)")
-    ap.add_argument("--trace-out", default=None, help="write the per-shape table of the instrumented step here")
-    ap.add_argument("--small", action="store_true", help="reduced widths/sizes (debug only, not the metric)")
-    ap.add_argument("--cfg5", action="store_true",
-                    help="BASELINE.json configs[4]: layout-conditioned (panorama ControlNet, 512x1024 condition image) -- not the metric line")
-    ap.add_argument("--cfg4", action="store_true",
-                    help="BASELINE.json configs[3]: 1024x2048 panorama (128x256 latent) + 20x512^2 views -- not the metric line")
-    args = ap.parse_args()
-
+def instrumented_step(args, model, loop, elapsed, rank):
+    """--full: one extra eager, single-stream step after the timed region with device events around every GEMM / attention
+    launch -> the `roofline` object of the result line (and the per-shape table of --trace-out)."""
     import torch
-    import torch.distributed as dist
     from panfusion_amd import ops
-    from panfusion_amd.models.sd2_unet_params import SD2_BASE
-    from panfusion_amd.pipeline import DenoiseLoop
-    from panfusion_amd.utils.pano import icosahedron_sample_camera
-    import numpy as np
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    assert world == args.gpus, "launch with torch.distributed.run --nproc-per-node == --gpus"
-    # PF_DIST_BACKEND=gloo + fewer GPUs than ranks: functional dry run of the sharded path on one GPU
-    backend = os.environ.get("PF_DIST_BACKEND", "nccl")
-    local = local % torch.cuda.device_count()
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev)
-        else:
-            dist.init_process_group(backend)
-
-    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
-    cfg = dict(SD2_BASE)
-    m, lat_hw, pano_hw, flop = 20, (64, 64), (64, 128), FLOP_PER_STEP_CFG2
-    workload = "cfg2: 512x1024 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes"
-    if args.cfg5:
-        flop = FLOP_PER_STEP_CFG2 + 2 * 0.66e12          # + ControlNet encoder + embedding per CFG sample
-        workload = "cfg5: cfg2 + panorama ControlNet on a 512x1024 layout condition (NOT the headline config)"
-    if args.cfg4:
-        pano_hw, flop = (128, 256), 64.36e12
-        workload = "cfg4: 1024x2048 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes (NOT the headline config)"
-    if args.small:
-        cfg.update(block_out_channels=(64, 128, 256, 256), num_heads=(1, 2, 4, 4), cross_attention_dim=128)
-        lat_hw, pano_hw, flop, workload = (16, 16), (16, 32), float("nan"), "debug-small"
-    th, ph = icosahedron_sample_camera()
-    cams_deg = (np.degrees(th), np.degrees(ph))
-
-    layout = None
-    if args.cfg5:       # the layout condition image of the panorama ControlNet (rolled with the panorama every step, PanFusion.py:150-153)
-        layout = (torch.rand(1, 1, 3, pano_hw[0] * 8, pano_hw[1] * 8, generator=torch.Generator().manual_seed(4)) * 2 - 1).to(dev)
-    if world > 1:
-        from panfusion_amd import sharding
-        model, loop = sharding.build_sharded(build_model, build_inputs, dev, dtype, cfg, m, lat_hw, pano_hw,
-                                             cams_deg, args.steps + args.warmup + 1, not args.no_graphs,
-                                             precision=args.precision, layout_cond=args.cfg5, layout=layout)
-    else:
-        model = build_model(dev, dtype, cfg, layout_cond=args.cfg5, precision=args.precision)
-        inputs = build_inputs(dev, m, lat_hw, pano_hw, cfg["cross_attention_dim"], cams_deg)
-        loop = DenoiseLoop(model, *inputs, steps=args.steps + args.warmup + 1, use_graphs=not args.no_graphs,
-                           pano_layout_cond=layout)
-
-    # PF_VIEW_PRIORITY=1 (experiment): the loop runs on a HIGH-priority stream; the panorama branch's side stream keeps the
-    # default priority, so its kernels fill the chip only where the view branch (the critical path) leaves it idle
-    import contextlib
-    hp = torch.cuda.stream(torch.cuda.Stream(dev, priority=-1)) if os.environ.get("PF_VIEW_PRIORITY") else contextlib.nullcontext()
-    with hp:
-        loop.prepare()                                    # tables + one graph per rotation offset, untimed
-        for _ in range(args.warmup):
-            loop.step()
-        if world > 1:
-            dist.barrier()
-            sharding.reset_comm()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loop.step()
-        torch.cuda.synchronize()
-    t_steps_done = time.perf_counter()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    distributed = None
-    if world > 1:
-        # what a SCALE record needs to check itself: the world this process group REALLY has, every rank's own time for the
-        # timed steps (before / without the closing barrier), what each collective moved
-        t_rank = torch.tensor([t_steps_done - t0], device=dev, dtype=torch.float64)
-        all_t = [torch.zeros_like(t_rank) for _ in range(world)]
-        dist.all_gather(all_t, t_rank)
-        per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in all_t]
-        tt = torch.tensor([elapsed], device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-        distributed = {"backend": dist.get_backend(), "world_size_initialised": dist.get_world_size(),
-                       "devices_visible": torch.cuda.device_count(),
-                       "rank_ms_per_step": {"min": min(per_rank_ms), "max": max(per_rank_ms), "per_rank": [round(v, 3) for v in per_rank_ms]},
-                       "layout": getattr(loop, "layout_desc", None),
-                       # hipGraph segments still in use after the run on EVERY rank (the fallback to eager launches is collective: a capture
-                       # that fails anywhere drops the graphs everywhere), and whether the EPA collectives were posted asynchronously
-                       "graphs_in_use": bool(getattr(loop, "use_graphs", False)), "async_collectives": bool(sharding.ASYNC),
-                       "collectives_rank0": sharding.comm_stats(args.steps),
-                       "note": "rank_ms = each rank's own wall time of the timed steps up to its final synchronize (no closing barrier); "
-                               "collectives: issued per step on rank 0, bytes = what that rank contributes per call"}
-
     # ---- instrumented step: device events around every GEMM / attention launch ------------------
     trace = []
     serial = getattr(model, "two_streams", None)
@@ -512,6 +402,150 @@ def main():
                                  for k, v in sorted(classes.items(), key=lambda kv: -kv[1][1])},
                     "other": {k: {"tflops": v[0] / v[1] / 1e12, "ms_per_step": v[1] * 1e3, "launches": v[2]}
                               for k, v in fam.items() if k != dom}}
+    return roofline
+
+
+def dump_outputs(loop, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of the loop receives it (DenoiseLoop.result():
+    the view latents and the panorama latent with the accumulated rotation undone), as out_dir/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lat, pano = loop.result()
+    for name, x in (("latents", lat), ("pano_latent", pano)):
+        np.save(os.path.join(out_dir, name + ".npy"), x.detach().float().cpu().numpy())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras: the instrumented step (`roofline`, --trace-out), the CPU baseline "
+                         "(`cpu_baseline`) and the training step (`training_step`); without it the run only sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the view latents and the panorama latent "
+                         "the loop returns) as DIR/latents.npy and DIR/pano_latent.npy, float32")
+    ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"],
+                    help="16-bit MFMA operand type.  fp16 (default) runs the MIXED scheme -- fp32 residual streams + "
+                         "split-precision stream-path GEMMs -- the configuration that meets north_star's 1e-3 parity bar "
+                         "(tests/test_gpu_mixed.py); bf16 runs the all-16-bit scheme of round 1 (1.2e-2), a labelled secondary line")
+    ap.add_argument("--precision", default=None, choices=["mixed", "fast"], help="override the scheme of --dtype")
+    ap.add_argument("--no-graphs", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-training-leg", action="store_true",
+                    help="with --full: skip the extra `training_step` measurement (N = 1 only; --no-cpu-baseline skips it too)")
+    ap.add_argument("--trace-out", default=None, help="with --full: write the per-shape table of the instrumented step here")
+    ap.add_argument("--small", action="store_true", help="reduced widths/sizes (debug only, not the metric)")
+    ap.add_argument("--cfg5", action="store_true",
+                    help="BASELINE.json configs[4]: layout-conditioned (panorama ControlNet, 512x1024 condition image) -- not the metric line")
+    ap.add_argument("--cfg4", action="store_true",
+                    help="BASELINE.json configs[3]: 1024x2048 panorama (128x256 latent) + 20x512^2 views -- not the metric line")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.trace_out and not args.full:
+        ap.error("--trace-out needs --full (the instrumented step is one of the extras)")
+
+    import torch
+    import torch.distributed as dist
+    from panfusion_amd.models.sd2_unet_params import SD2_BASE
+    from panfusion_amd.pipeline import DenoiseLoop
+    from panfusion_amd.utils.pano import icosahedron_sample_camera
+    import numpy as np
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    assert world == args.gpus, "launch with torch.distributed.run --nproc-per-node == --gpus"
+    # PF_DIST_BACKEND=gloo + fewer GPUs than ranks: functional dry run of the sharded path on one GPU
+    backend = os.environ.get("PF_DIST_BACKEND", "nccl")
+    local = local % torch.cuda.device_count()
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world > 1:
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    cfg = dict(SD2_BASE)
+    m, lat_hw, pano_hw, flop = 20, (64, 64), (64, 128), FLOP_PER_STEP_CFG2
+    workload = "cfg2: 512x1024 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes"
+    if args.cfg5:
+        flop = FLOP_PER_STEP_CFG2 + 2 * 0.66e12          # + ControlNet encoder + embedding per CFG sample (SURVEY.md §8 a21)
+        workload = "cfg5: cfg2 + panorama ControlNet on a 512x1024 layout condition (NOT the headline config)"
+    if args.cfg4:
+        pano_hw, flop = (128, 256), 64.36e12
+        workload = "cfg4: 1024x2048 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes (NOT the headline config)"
+    if args.small:
+        cfg.update(block_out_channels=(64, 128, 256, 256), num_heads=(1, 2, 4, 4), cross_attention_dim=128)
+        lat_hw, pano_hw, flop, workload = (16, 16), (16, 32), float("nan"), "debug-small"
+    th, ph = icosahedron_sample_camera()
+    cams_deg = (np.degrees(th), np.degrees(ph))
+
+    layout = None
+    if args.cfg5:       # the layout condition image of the panorama ControlNet (rolled with the panorama every step, PanFusion.py:150-153)
+        layout = (torch.rand(1, 1, 3, pano_hw[0] * 8, pano_hw[1] * 8, generator=torch.Generator().manual_seed(4)) * 2 - 1).to(dev)
+    if world > 1:
+        from panfusion_amd import sharding
+        model, loop = sharding.build_sharded(build_model, build_inputs, dev, dtype, cfg, m, lat_hw, pano_hw,
+                                             cams_deg, args.steps + args.warmup + 1, not args.no_graphs,
+                                             precision=args.precision, layout_cond=args.cfg5, layout=layout)
+    else:
+        model = build_model(dev, dtype, cfg, layout_cond=args.cfg5, precision=args.precision)
+        inputs = build_inputs(dev, m, lat_hw, pano_hw, cfg["cross_attention_dim"], cams_deg)
+        loop = DenoiseLoop(model, *inputs, steps=args.steps + args.warmup + 1, use_graphs=not args.no_graphs,
+                           pano_layout_cond=layout)
+
+    # PF_VIEW_PRIORITY=1 (experiment): the loop runs on a HIGH-priority stream; the panorama branch's side stream keeps the
+    # default priority, so its kernels fill the chip only where the view branch (the critical path) leaves it idle
+    import contextlib
+    hp = torch.cuda.stream(torch.cuda.Stream(dev, priority=-1)) if os.environ.get("PF_VIEW_PRIORITY") else contextlib.nullcontext()
+    with hp:
+        loop.prepare()                                    # tables + one graph per rotation offset, untimed
+        for _ in range(args.warmup):
+            loop.step()
+        if world > 1:
+            dist.barrier()
+            sharding.reset_comm()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loop.step()
+        torch.cuda.synchronize()
+    t_steps_done = time.perf_counter()
+    if world > 1:
+        dist.barrier()
+    elapsed = time.perf_counter() - t0
+    distributed = None
+    if world > 1:
+        # what a SCALE record needs to check itself: the world this process group REALLY has, every rank's own time for the
+        # timed steps (before / without the closing barrier), what each collective moved
+        t_rank = torch.tensor([t_steps_done - t0], device=dev, dtype=torch.float64)
+        all_t = [torch.zeros_like(t_rank) for _ in range(world)]
+        dist.all_gather(all_t, t_rank)
+        per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in all_t]
+        tt = torch.tensor([elapsed], device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+        distributed = {"backend": dist.get_backend(), "world_size_initialised": dist.get_world_size(),
+                       "devices_visible": torch.cuda.device_count(),
+                       "rank_ms_per_step": {"min": min(per_rank_ms), "max": max(per_rank_ms), "per_rank": [round(v, 3) for v in per_rank_ms]},
+                       "layout": getattr(loop, "layout_desc", None),
+                       # hipGraph segments still in use after the run on EVERY rank (the fallback to eager launches is collective: a capture
+                       # that fails anywhere drops the graphs everywhere), and whether the EPA collectives were posted asynchronously
+                       "graphs_in_use": bool(getattr(loop, "use_graphs", False)), "async_collectives": bool(sharding.ASYNC),
+                       "collectives_rank0": sharding.comm_stats(args.steps),
+                       "note": "rank_ms = each rank's own wall time of the timed steps up to its final synchronize (no closing barrier); "
+                               "collectives: issued per step on rank 0, bytes = what that rank contributes per call"}
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, args.dump_outputs)
+    roofline = instrumented_step(args, model, loop, elapsed, rank) if args.full else None
 
     if rank == 0:
         metric = ("DDIM denoise steps/sec, 1024x2048 pano + 20x512^2 views (configs[3])" if args.cfg4
@@ -527,15 +561,16 @@ def main():
                               "mixed": "mixed scheme: fp32 residual streams + split-precision stream-path GEMMs (<= 1e-3 rel-L2 vs the fp32 oracle)",
                               "fast": "all activations 16-bit (parity 1.7e-3 fp16 / 1.2e-2 bf16: does NOT meet the 1e-3 bar)"}[model.precision]),
                           "parallelism": "single" if world == 1 else getattr(loop, "layout_desc", "sharded")},
-               "tflops_per_step": flop / 1e12, "frac_of_mfma_ceiling": (flop * args.steps / elapsed) / (PEAK_BF16_DENSE_TFLOPS * 1e12),
-               "roofline": roofline}
+               "tflops_per_step": flop / 1e12, "frac_of_mfma_ceiling": (flop * args.steps / elapsed) / (PEAK_BF16_DENSE_TFLOPS * 1e12)}
+        if args.full:
+            res["roofline"] = roofline
         if distributed is not None:
             res["distributed"] = distributed
-        if not args.no_cpu_baseline and world == 1 and not args.small:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.small:
             res["cpu_baseline"] = cpu_baseline(cfg, cfg["cross_attention_dim"], lat_hw, pano_hw, m, cams_deg, flop)
         # (skipped with --no-cpu-baseline as well: that flag marks the quick / profiled runs of tools/*.sh -- under
         # rocprofv3 --pmc the ~6000 launches of a training step take tens of minutes)
-        if not args.no_training_leg and not args.no_cpu_baseline and world == 1 and not (args.small or args.cfg4 or args.cfg5):
+        if args.full and not args.no_training_leg and not args.no_cpu_baseline and world == 1 and not (args.small or args.cfg4 or args.cfg5):
             # extra, after the metric and its baseline: the training step through the same boundary
             try:
                 del loop, model

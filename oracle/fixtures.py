@@ -199,3 +199,77 @@ def chunked_attention():
         finally:
             U.Attention.forward, MV._BiasedCrossAttention.forward = saved, saved_epa
     return ctx()
+
+
+# ---- storage of the fixtures under tests/golden/ ---------------------------------------------------------------------
+# A committed file stays under 1 MiB: a fixture whose arrays hold more than PART_BYTES is written as <stem>.part0.npz,
+# <stem>.part1.npz, ... and an array larger than that as flat chunks (<key>.chunk0, <key>.chunk1, ... + <key>.shape).
+PART_BYTES = 768 << 10
+
+
+def _part(path, k):
+    return "%s.part%d.npz" % (path[:-len(".npz")], k)
+
+
+def golden_exists(path):
+    """Whether the fixture ``.../name.npz`` exists, whole or in parts."""
+    import os
+    return os.path.exists(path) or os.path.exists(_part(path, 0))
+
+
+def save_golden(path, **arrays):
+    """``np.savez_compressed(path, **arrays)``, split into parts of at most PART_BYTES of array data when larger."""
+    import os
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    k = 0
+    while os.path.exists(_part(path, k)):             # a previous split of the same fixture
+        os.remove(_part(path, k))
+        k += 1
+    if sum(a.nbytes for a in arrays.values()) <= PART_BYTES:
+        np.savez_compressed(path, **arrays)
+        return
+    if os.path.exists(path):
+        os.remove(path)
+    entries = []
+    for key, a in arrays.items():
+        if a.nbytes <= PART_BYTES:
+            entries.append((key, a))
+            continue
+        flat, n = np.ascontiguousarray(a).reshape(-1), max(1, PART_BYTES // a.itemsize)
+        entries.append((key + ".shape", np.array(a.shape, dtype=np.int64)))
+        entries += [("%s.chunk%d" % (key, j), flat[i:i + n]) for j, i in enumerate(range(0, flat.size, n))]
+    parts, cur, size = [], {}, 0
+    for key, a in entries:
+        if cur and size + a.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[key] = a
+        size += a.nbytes
+    parts.append(cur)
+    for k, part in enumerate(parts):
+        np.savez_compressed(_part(path, k), **part)
+
+
+def load_golden(path):
+    """The arrays of a fixture written by save_golden (or by np.savez_compressed), as a dict name -> array."""
+    import os
+    if os.path.exists(path):
+        with np.load(path) as z:
+            return {k: z[k] for k in z.files}
+    if not os.path.exists(_part(path, 0)):
+        raise FileNotFoundError(path)
+    raw, k = {}, 0
+    while os.path.exists(_part(path, k)):
+        with np.load(_part(path, k)) as z:
+            raw.update((key, z[key]) for key in z.files)
+        k += 1
+    out = {}
+    for key in [key for key in raw if not key.endswith(".shape") and ".chunk" not in key]:
+        out[key] = raw[key]
+    for key in [key[:-len(".shape")] for key in raw if key.endswith(".shape")]:
+        chunks, j = [], 0
+        while "%s.chunk%d" % (key, j) in raw:
+            chunks.append(raw["%s.chunk%d" % (key, j)])
+            j += 1
+        out[key] = np.concatenate(chunks).reshape(tuple(raw[key + ".shape"]))
+    return out

@@ -45,7 +45,19 @@ def pytest_collection_modifyitems(config, items):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name))
+    from oracle.fixtures import load_golden
+    return load_golden(os.path.join(GOLDEN, name))
+
+
+def assert_within_one_ulp(got, want, max_frac=1e-3):
+    """Float32 values that must agree exactly up to the host's sin / cos rounding: every element within one unit in the
+    last place, and at most ``max_frac`` of them not bit-identical."""
+    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    ulp = np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64))
+    ulp[(got == want)] = 0                                        # +0.0 / -0.0
+    assert int(ulp.max()) <= 1, int(ulp.max())
+    assert float((ulp > 0).mean()) <= max_frac, float((ulp > 0).mean())
 
 
 def rel_l2(a, b):

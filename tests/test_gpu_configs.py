@@ -17,14 +17,15 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, rel_l2
+from conftest import GOLDEN, golden, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
 def _have(name):
-    return os.path.exists(os.path.join(GOLDEN, name))
+    from oracle.fixtures import golden_exists
+    return golden_exists(os.path.join(GOLDEN, name))
 
 
 def _hip_model(om, controlnet=False):
@@ -54,7 +55,7 @@ def test_cfg2_headline_config_vs_oracle(full_oracle):
     after every one of the 7 blocks on 8-channel slices, then both epsilon outputs at <= 1e-3."""
     from oracle import fixtures as FX
     from panfusion_amd.models.pano.modules import WarpAttn
-    gd = np.load(os.path.join(GOLDEN, "cfg2_eps.npz"))
+    gd = golden("cfg2_eps.npz")
     model = _hip_model(full_oracle)
     args = FX.first_step_call(FX.ico_cameras(), (64, 64), (64, 128), cfg_pair=True)
     got = {}
@@ -91,7 +92,7 @@ def test_cfg2_headline_config_vs_oracle(full_oracle):
     # ... and against the fixture the REFERENCE CLASS itself produced for the conditional half (tools/make_golden_cfg.py cfg2ref:
     # models/pano/MVGenModel.py:38-297 with its own WarpAttn / get_masks / dense per-head bias, 3.0e-6 / 2.5e-6 from the port's file)
     if _have("cfg2_ref_cond.npz"):
-        gr = np.load(os.path.join(GOLDEN, "cfg2_ref_cond.npz"))
+        gr = golden("cfg2_ref_cond.npz")
         rv, rp = rel_l2(s[1:].cpu(), torch.from_numpy(gr["sample"])), rel_l2(ps[1:].cpu(), torch.from_numpy(gr["pano_sample"]))
         print("  conditional half vs the reference class's own output: views %.3e  pano %.3e" % (rv, rp))
         assert rv <= 1e-3 and rp <= 1e-3, (rv, rp)
@@ -102,7 +103,7 @@ def test_cfg2_late_step_second_rotation_vs_oracle(full_oracle):
     """The headline configuration again (m = 20 x CFG pair) at a LATE iteration of the loop: timestep t = 21, cameras and
     panorama at 180 degrees of accumulated rotation (another table set, another region of the timestep embedding)."""
     from oracle import fixtures as FX
-    gd = np.load(os.path.join(GOLDEN, "cfg2b_eps.npz"))
+    gd = golden("cfg2b_eps.npz")
     model = _hip_model(full_oracle)
     args = FX.first_step_call(FX.ico_cameras(), (64, 64), (64, 128), cfg_pair=True, t=21, rot=180.0)
     s, ps = _call(model, args)
@@ -122,7 +123,7 @@ def test_cfg1_ten_ddim_steps_vs_oracle(full_oracle, graphs):
     from oracle import fixtures as FX
     from panfusion_amd import ops
     from panfusion_amd.pipeline import DenoiseLoop
-    gd = np.load(os.path.join(GOLDEN, "cfg1_ddim10.npz"))
+    gd = golden("cfg1_ddim10.npz")
     model = _hip_model(full_oracle)
     cams = FX.horizon4_cameras()
     latents, pano_latent, pe, ppe = FX.loop_inputs(cams, (32, 32), (64, 128))
@@ -158,7 +159,7 @@ def _against_reference_class(name, s, ps):
     (tools/make_golden_cfg.py cfg4ref / cfg5ref; the port equals it to fp32 round-off: tests/test_oracle_golden.py)."""
     if not _have(name):
         return
-    gr = np.load(os.path.join(GOLDEN, name))
+    gr = golden(name)
     rv, rp = rel_l2(s[1:].cpu(), torch.from_numpy(gr["sample"])), rel_l2(ps[1:].cpu(), torch.from_numpy(gr["pano_sample"]))
     print("  conditional half vs the reference class's own output (%s): views %.3e  pano %.3e" % (name, rv, rp))
     assert rv <= 1e-3 and rp <= 1e-3, (name, rv, rp)
@@ -172,7 +173,7 @@ def test_cfg1_range_stress_vs_oracle():
     channel.  fp16 operands have 5 exponent bits: the default path must stay finite and within the same 1e-3 of the fp32 oracle
     (reference class as denoiser, tools/make_golden_cfg.py cfg1s) on cfg 1's first denoiser call, CFG pair, SD-2-base widths."""
     from oracle import fixtures as FX
-    gd = np.load(os.path.join(GOLDEN, "cfg1_stress_eps.npz"))
+    gd = golden("cfg1_stress_eps.npz")
     assert float(gd["stream_peaks"].max()) >= 1e3, "the fixture must actually stress the range"
     om = FX.build_full_width()
     FX.apply_range_stress(om)
@@ -190,7 +191,7 @@ def test_cfg1_range_stress_vs_oracle():
 def test_cfg4_large_panorama_vs_oracle(full_oracle):
     """BASELINE.json configs[3]: 1024x2048 panorama (128x256 latent, 32 768 self-attention tokens) + 20 views, the CFG pair."""
     from oracle import fixtures as FX
-    gd = np.load(os.path.join(GOLDEN, "cfg4_eps.npz"))
+    gd = golden("cfg4_eps.npz")
     model = _hip_model(full_oracle)
     args = FX.first_step_call(FX.ico_cameras(), (64, 64), (128, 256), cfg_pair=True)
     s, ps = _call(model, args)
@@ -205,7 +206,7 @@ def test_cfg5_layout_controlnet_vs_oracle():
     """BASELINE.json configs[4]: cfg 2's geometry + the panorama ControlNet at SD-2-base widths on a 512x1024 layout image,
     the CFG pair (the condition image duplicated as gen_cls_free_guide_pair does, PanoGenerator.py:240-251)."""
     from oracle import fixtures as FX
-    gd = np.load(os.path.join(GOLDEN, "cfg5_eps.npz"))
+    gd = golden("cfg5_eps.npz")
     om = FX.build_full_width(controlnet=True)
     model = _hip_model(om, controlnet=True)
     args = FX.first_step_call(FX.ico_cameras(), (64, 64), (64, 128), cfg_pair=True)

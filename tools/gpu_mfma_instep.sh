@@ -9,8 +9,8 @@ R=$GRAFT_REPO_ROOT
 TAG=${1:-r4}
 cd /tmp
 rm -rf /tmp/mi1 /tmp/mi2
-PF_STREAMS=1 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d /tmp/mi1 -o g -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-training-leg --no-graphs > $R/gpurun_out/${TAG}_mfma_instep_1.log 2>&1
-PF_STREAMS=1 timeout 900 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/mi2 -o g -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-training-leg --no-graphs > $R/gpurun_out/${TAG}_mfma_instep_2.log 2>&1
+PF_STREAMS=1 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $PWD/mi1 -o g -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-training-leg --no-graphs > $PWD/${TAG}_mfma_instep_1.log 2>&1
+PF_STREAMS=1 timeout 900 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $PWD/mi2 -o g -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-training-leg --no-graphs > $PWD/${TAG}_mfma_instep_2.log 2>&1
 python - $(find /tmp/mi1 -name '*counter_collection.csv' | head -1) $(find /tmp/mi2 -name '*counter_collection.csv' | head -1) $R/gpurun_out/${TAG}_mfma_instep.txt $R <<'PY'
 import csv, re, sys
 from collections import defaultdict

@@ -28,7 +28,7 @@ export TMPDIR=/tmp
 ulimit -c 0
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-run}; shift
-NOLEGS="--no-cpu-baseline --no-training-leg"
+NOLEGS="--full --no-cpu-baseline --no-training-leg"
 q() { grep -v amdgpu.ids; }
 line() { tail -n 1 "$1" | python -c "
 import sys, json
@@ -65,7 +65,7 @@ for SEC in "$@"; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | q | tail -n 3 | tee gpurun_out/${TAG}_smoke.log ;;
     bench)
       S=$(slug "$ARG"); F=gpurun_out/${TAG}_bench${S:+_$S}
-      timeout 900 python bench.py $ARG --trace-out gpurun_out/${TAG}_shapes${S:+_$S}.txt > $F.log 2>&1
+      timeout 900 python bench.py --full $ARG --trace-out ${F%/*}/${TAG}_shapes${S:+_$S}.txt > $F.log 2>&1
       tail -n 1 $F.log > $F.json; line $F.json "bench $ARG" ;;
     env)
       { run() { env $1 python bench.py $NOLEGS --steps 10 --warmup 2 2>&1 | tail -n 1 > /tmp/l.json; line /tmp/l.json "$1"; }

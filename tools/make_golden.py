@@ -23,6 +23,7 @@ from oracle import geometry as G  # noqa: E402
 from oracle import mvgen as MV  # noqa: E402
 from oracle import ref_import  # noqa: E402
 from oracle import sd2_unet as U  # noqa: E402
+from oracle.fixtures import save_golden  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 TINY = dict(width=64, cross_attention_dim=128, heads=(1, 2, 4, 4), groups=32)
@@ -99,7 +100,7 @@ def main():
     nz = lambda a: (a.reshape(-1).nonzero().flatten().numpy().astype(np.int32), a.reshape(-1)[a.reshape(-1) != 0].numpy())
     pm4i, pm4v = nz(pm4 + 1)
     em4i, em4v = nz(em4 + 1)
-    np.savez_compressed(os.path.join(OUT, "epa_tables.npz"), pers_masks=pm.numpy(), equi_masks=em.numpy(),
+    save_golden(os.path.join(OUT, "epa_tables.npz"), pers_masks=pm.numpy(), equi_masks=em.numpy(),
                         pers_coords=pc.numpy(), equi_coords=ec.numpy(),
                         pe80_pers=pe80(pc).numpy(), pe80_equi=pe80(ec).numpy(),
                         pe320_equi=pe320(ec).numpy(), freq80=pe80.freq_bands.numpy(),

@@ -71,7 +71,7 @@ def cfg2():
     print("cfg2 oracle forward %.0f s" % (time.time() - t0), flush=True)
     for h in hooks:
         h.remove()
-    np.savez_compressed(os.path.join(OUT, "cfg2_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy(), **got)
+    FX.save_golden(os.path.join(OUT, "cfg2_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy(), **got)
 
 
 def cfg2ref():
@@ -88,11 +88,11 @@ def cfg2ref():
     t0 = time.time()
     s, ps = call(rm, args)
     print("cfg2ref reference forward (one CFG half) %.0f s" % (time.time() - t0), flush=True)
-    old = np.load(os.path.join(OUT, "cfg2_eps.npz"))
+    old = FX.load_golden(os.path.join(OUT, "cfg2_eps.npz"))
     rel = lambda a, b: float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
     d_v, d_p = rel(old["sample"][1:], s.numpy()), rel(old["pano_sample"][1:], ps.numpy())
     print("cfg2ref: port-generated cfg2_eps.npz (conditional half) vs the reference class: %.2e views / %.2e panorama" % (d_v, d_p), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg2_ref_cond.npz"), sample=s.numpy(), pano_sample=ps.numpy(),
+    FX.save_golden(os.path.join(OUT, "cfg2_ref_cond.npz"), sample=s.numpy(), pano_sample=ps.numpy(),
                         port_vs_reference=np.array([d_v, d_p]))
 
 
@@ -109,11 +109,11 @@ def _ref_cond(name, fixture, out, pano_hw, controlnet=False):
     t0 = time.time()
     s, ps = call(rm, args, **extra)
     print("%s reference forward (one CFG half) %.0f s" % (name, time.time() - t0), flush=True)
-    old = np.load(os.path.join(OUT, fixture))
+    old = FX.load_golden(os.path.join(OUT, fixture))
     rel = lambda a, b: float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
     d_v, d_p = rel(old["sample"][1:], s.numpy()), rel(old["pano_sample"][1:], ps.numpy())
     print("%s: port-generated %s (conditional half) vs the reference class: %.2e views / %.2e panorama" % (name, fixture, d_v, d_p), flush=True)
-    np.savez_compressed(os.path.join(OUT, out), sample=s.numpy(), pano_sample=ps.numpy(), port_vs_reference=np.array([d_v, d_p]))
+    FX.save_golden(os.path.join(OUT, out), sample=s.numpy(), pano_sample=ps.numpy(), port_vs_reference=np.array([d_v, d_p]))
 
 
 def cfg2bref():
@@ -124,11 +124,11 @@ def cfg2bref():
     t0 = time.time()
     s, ps = call(rm, args)
     print("cfg2bref reference forward (one CFG half) %.0f s" % (time.time() - t0), flush=True)
-    old = np.load(os.path.join(OUT, "cfg2b_eps.npz"))
+    old = FX.load_golden(os.path.join(OUT, "cfg2b_eps.npz"))
     rel = lambda a, b: float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
     d_v, d_p = rel(old["sample"][1:], s.numpy()), rel(old["pano_sample"][1:], ps.numpy())
     print("cfg2bref: port-generated cfg2b_eps.npz (conditional half) vs the reference class: %.2e views / %.2e panorama" % (d_v, d_p), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg2b_ref_cond.npz"), sample=s.numpy(), pano_sample=ps.numpy(), port_vs_reference=np.array([d_v, d_p]))
+    FX.save_golden(os.path.join(OUT, "cfg2b_ref_cond.npz"), sample=s.numpy(), pano_sample=ps.numpy(), port_vs_reference=np.array([d_v, d_p]))
 
 
 def cfg4ref():
@@ -147,7 +147,7 @@ def cfg2b():
     t0 = time.time()
     s, ps = call(model, args)
     print("cfg2b oracle forward %.0f s" % (time.time() - t0), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg2b_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
+    FX.save_golden(os.path.join(OUT, "cfg2b_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
 
 
 def cfg1():
@@ -168,7 +168,7 @@ def cfg1():
             traj_v.append(latents.numpy().copy())
             traj_p.append(oddim.rotate_latent(pano_latent, cams, -total)[0].numpy().copy())     # un-rotated frame
             print("cfg1 step t=%d  %.0f s" % (int(t), time.time() - t0), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg1_ddim10.npz"), latents=np.stack(traj_v), pano_latent=np.stack(traj_p))
+    FX.save_golden(os.path.join(OUT, "cfg1_ddim10.npz"), latents=np.stack(traj_v), pano_latent=np.stack(traj_p))
 
 
 def cfg1s():
@@ -199,7 +199,7 @@ def cfg1s():
     top = sorted(peaks.items(), key=lambda kv: -kv[1])[:5]
     print("cfg1s: largest |stream| values:", ", ".join("%s %.3g" % kv for kv in top), flush=True)
     print("cfg1s: eps finite:", bool(torch.isfinite(s).all() and torch.isfinite(ps).all()), " |eps| rms %.3g / %.3g" % (float(s.pow(2).mean().sqrt()), float(ps.pow(2).mean().sqrt())))
-    np.savez_compressed(os.path.join(OUT, "cfg1_stress_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy(),
+    FX.save_golden(os.path.join(OUT, "cfg1_stress_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy(),
                         stream_names=np.array(names), stream_peaks=np.array([peaks[n] for n in names], dtype=np.float32))
 
 
@@ -209,7 +209,7 @@ def cfg4():
     t0 = time.time()
     s, ps = call(model, args)
     print("cfg4 oracle forward %.0f s" % (time.time() - t0), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg4_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
+    FX.save_golden(os.path.join(OUT, "cfg4_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
 
 
 def cfg5():
@@ -220,7 +220,7 @@ def cfg5():
     t0 = time.time()
     s, ps = call(model, args, pano_layout_cond=cond)
     print("cfg5 oracle forward %.0f s" % (time.time() - t0), flush=True)
-    np.savez_compressed(os.path.join(OUT, "cfg5_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
+    FX.save_golden(os.path.join(OUT, "cfg5_eps.npz"), sample=s.numpy(), pano_sample=ps.numpy())
 
 
 if __name__ == "__main__":
