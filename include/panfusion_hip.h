@@ -235,6 +235,24 @@ pf_status pf_cfg_ddim_step_pair(const float* x, const float* eps_uncond, const f
                                 float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
                                 int64_t* tstep, int n_tstep, int64_t t_next, void* stream);
 
+/* pf_cfg_ddim_step_pair with the DPM-Solver++(2M) multistep update (diffusers DPMSolverMultistepScheduler,
+ * algorithm_type="dpmsolver++", solver_order=2, solver_type="midpoint": multistep_dpm_solver_second_order_update) in the
+ * loop of PanFusion.py:146-162.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log alpha - log sigma, s0 = the current
+ * timestep, t = its target, s1 = the previous step's timestep, h = lambda_t - lambda_s0, r0 = (lambda_s0 - lambda_s1) / h:
+ *   x_t = (sigma_t/sigma_s0) x - alpha_t (e^-h - 1) D0 - 1/2 alpha_t (e^-h - 1) D1,  D0 = x0, D1 = (x0 - x0_prev) / r0
+ * whose first two terms are the DDIM update; the kernel computes
+ *   out = DDIM(x, eps) + k (x0 - x0_prev),  k = 1/2 alpha_t (1 - e^-h) / r0  (host: float64, passed as fp32)
+ * with eps, x0 and DDIM(x, eps) in the operation sequence of pf_cfg_ddim_step_pair, and writes x0 to x0_out[(w + roll) mod W]
+ * -- the history rolls with the state, into the frame of the next call.  x0_prev == NULL: a first-order step (k unused, the
+ * history not read), out bit-identical to pf_cfg_ddim_step_pair.  Two rows staged in LDS: W <= 8192.  out may alias x and
+ * x0_out may alias x0_prev for any roll; x0_out (required) must not alias x, the predictions, out or out2; x0_prev must not
+ * alias out / out2.  x0_prev / x0_out fp32, the shape of x. */
+pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
+                                 float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
+                                 float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
+                                 int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                 float* x0_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MFMA GEMM / implicit-GEMM convolution (replaces cuDNN/cuBLAS behind diffusers Conv2d/Linear:
  * MVGenModel.py:86-144,174-198,224-294 and transformer.py:57-74,8-38).

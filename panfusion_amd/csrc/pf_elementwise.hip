@@ -1,14 +1,14 @@
 // HBM-bound kernels of the denoising path for gfx950: GroupNorm statistics / apply(+SiLU),
 // LayerNorm(+positional encoding), GEGLU, timestep features, circular width pad / crop, layout
-// converters, CFG+DDIM update, and the two 4-channel boundary convolutions.
+// converters, CFG+DDIM / DPM-Solver++(2M) updates, and the two 4-channel boundary convolutions.
 //
 // All activations are NHWC 16-bit, moved as 16-byte (8-element) vectors; statistics are fp32
 // (fp64 for the final GroupNorm moments); reductions are wavefront (64-lane) shuffles.
 //
 // Reference call sites: diffusers ResnetBlock2D / Transformer2DModel driven from
 // models/pano/MVGenModel.py:98-294; models/modules/transformer.py:8-38,151-162;
-// utils/pano.py:74-105; models/pano/PanoGenerator.py:253-269; DDIMScheduler.step
-// (models/pano/PanFusion.py:159-162).
+// utils/pano.py:74-105; models/pano/PanoGenerator.py:253-269; DDIMScheduler.step /
+// DPMSolverMultistepScheduler.step (models/pano/PanFusion.py:159-162).
 #include "pf_common.h"
 #include <stdlib.h>
 #include <math.h>
@@ -594,6 +594,47 @@ __global__ __launch_bounds__(256) void k_cfg_ddim_rows(const float* x, const flo
         const float v = row[w];
         out[base + w] = v;
         if (out2) out2[base + w] = v;
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
+}
+
+// ---- CFG + DPM-Solver++(2M) ------------------------------------------------------------------
+// cfg_ddim_value's operation sequence, x0 returned too: a first-order step stays bit-identical to the DDIM kernels
+__device__ __forceinline__ float cfg_ddim_value_x0(float x, float u, float c, float g, float sa, float sb, float sap, float sbp,
+                                                   float& x0) {
+    const float eps = __builtin_fmaf(g, c - u, u);
+    x0 = __builtin_fmaf(-sb, eps, x) / sa;
+    return __builtin_fmaf(sap, x0, sbp * eps);
+}
+
+// k_cfg_ddim_rows plus the multistep correction x' = DDIM(x, eps) + k (x0 - x0_prev) (x0_prev == NULL: first order, k unused);
+// the state row and the x0 row are staged in LDS at their rolled positions, so out may alias x and x0_out may alias x0_prev
+// for ANY roll (every block reads its rows in full before the barrier and writes them after it)
+__global__ __launch_bounds__(256) void k_cfg_dpmpp_rows(const float* x, const float* __restrict__ eu,
+                                                        const float* __restrict__ ec, float g, float sa, float sb, float sap,
+                                                        float sbp, const float* x0_prev, float k, int W, int roll, float* out,
+                                                        float* out2, float* x0_out, long long* tstep, int n_tstep,
+                                                        long long t_next) {
+    extern __shared__ float stage[];
+    float* row = stage;
+    float* row_x0 = stage + W;
+    const long base = static_cast<long>(blockIdx.x) * W;
+    for (int w = threadIdx.x; w < W; w += 256) {
+        int wo = w + roll;
+        wo -= wo >= W ? W : 0;
+        float x0;
+        float v = cfg_ddim_value_x0(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp, x0);
+        if (x0_prev) v = __builtin_fmaf(k, x0 - x0_prev[base + w], v);
+        row[wo] = v;
+        row_x0[wo] = x0;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+        x0_out[base + w] = row_x0[w];
     }
     if (tstep && blockIdx.x == 0)
         for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
@@ -1336,6 +1377,26 @@ extern "C" pf_status pf_cfg_ddim_step_pair(const float* x, const float* eu, cons
     hipLaunchKernelGGL(k_cfg_ddim_rows, dim3(static_cast<unsigned>(rows)), dim3(256), static_cast<size_t>(W) * sizeof(float), as_stream(stream),
                        x, eu, ec, g, sa, sb, sap, sbp, W, r, out, out2, reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
     PF_CHECK_LAUNCH("pf_cfg_ddim_step_pair");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb, float sap,
+                                            float sbp, long rows, int W, int roll, float* out, float* out2,
+                                            int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                            float* x0_out, void* stream) {
+    PF_REQUIRE(x && eu && ec && out && x0_out && rows > 0 && W > 0, "pf_cfg_dpmpp_step_pair: bad arguments (x0_out is required)");
+    PF_REQUIRE(rows < (1L << 31) && W <= 8192, "pf_cfg_dpmpp_step_pair: rows=%ld must be < 2^31 and W=%d <= 8192 (one row per block, two rows staged in LDS)", rows, W);
+    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_dpmpp_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
+    PF_REQUIRE(x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2,
+               "pf_cfg_dpmpp_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
+    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_dpmpp_step_pair: x0_prev must not alias out / out2");
+    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_dpmpp_step_pair: n_tstep must be positive with tstep");
+    int r = roll % W;
+    if (r < 0) r += W;
+    hipLaunchKernelGGL(k_cfg_dpmpp_rows, dim3(static_cast<unsigned>(rows)), dim3(256), 2 * static_cast<size_t>(W) * sizeof(float),
+                       as_stream(stream), x, eu, ec, g, sa, sb, sap, sbp, x0_prev, k, W, r, out, out2, x0_out,
+                       reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
+    PF_CHECK_LAUNCH("pf_cfg_dpmpp_step_pair");
     return PF_OK;
 }
 

@@ -447,6 +447,30 @@ def cfg_ddim_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None
     return out
 
 
+def cfg_dpmpp_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0,
+                        x0_prev=None, k=0.0, x0_out=None):
+    """cfg_ddim_step_pair with the DPM-Solver++(2M) correction: out = DDIM(x, eps) + k (x0 - x0_prev), and this step's x0 written
+    to ``x0_out`` at the rolled position (the next step's history).  ``x0_prev=None``: a first-order step, out bit-identical to
+    cfg_ddim_step_pair.  ``x0_out`` may be ``x0_prev`` itself; returns (out, x0_out)."""
+    W = x.shape[-1]
+    rows = x.numel() // W
+    if out is None:
+        out = torch.empty_like(x)
+    if x0_out is None:
+        x0_out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and x0_out.is_contiguous() and (out2 is None or out2.is_contiguous())
+    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
+    assert x0_out.dtype == torch.float32 and x0_out.numel() == x.numel()
+    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    sa, sb, sap, sbp = (float(c) for c in coef)
+    check(_lib.lib().pf_cfg_dpmpp_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
+                                            rows, W, int(roll), _p(out), _p(out2) if out2 is not None else None,
+                                            _p(tstep) if tstep is not None else None, tstep.numel() if tstep is not None else 0,
+                                            int(t_next), _p(x0_prev) if x0_prev is not None else None, float(k), _p(x0_out),
+                                            _stream()), "pf_cfg_dpmpp_step_pair")
+    return out, x0_out
+
+
 # ---------------------------------------------------------------------------- GEMM / conv
 def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, stride=1, pad=0, upsample=0,
               bias=None, rowvec=None, residual=None, out=None, out_dtype=None, batch=1,

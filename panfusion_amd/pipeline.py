@@ -6,8 +6,12 @@ one loop iteration -- 90-degree latent roll, CFG-paired dual-branch denoiser,
 CFG merge, two DDIM updates -- per ``step()``.  The denoiser call can be
 captured into one hipGraph per rotation offset (the geometry is 4-periodic,
 SURVEY.md §4) and replayed; the CFG+DDIM update is a separate fused kernel
-whose scalar coefficients change every step.
+whose scalar coefficients change every step.  ``sampler="dpmpp_2m"`` swaps the
+update for DPM-Solver++(2M) on the same timestep grid (``DPMSolverSchedule``,
+DESIGN.md §4.5); DDIM stays the default.
 """
+import copy
+import math
 import os
 
 import torch
@@ -39,6 +43,76 @@ class DDIMSchedule:
         return (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_prev ** 0.5), float((1 - a_prev) ** 0.5))
 
 
+class DPMSolverSchedule:
+    """DPM-Solver++(2M) (diffusers DPMSolverMultistepScheduler, algorithm_type="dpmsolver++", solver_type="midpoint") on
+    DDIMSchedule's grid and alphas_cumprod: leading spacing, steps_offset 1, the target of step t is t - 1000 // n, the last
+    step targets alphas_cumprod[0] (set_alpha_to_one=False).
+
+    With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log alpha - log sigma, s0 = timesteps[i], t = its target and
+    s1 = timesteps[i - 1], diffusers' second-order update
+        x_t = (sigma_t / sigma_s0) x - alpha_t (e^-h - 1) D0 - 1/2 alpha_t (e^-h - 1) D1,  D0 = x0, D1 = (x0 - x0_prev) / r0,
+        h = lambda_t - lambda_s0,  r0 = (lambda_s0 - lambda_s1) / h
+    is DDIM(x, eps) (its first two terms) + k (x0 - x0_prev) with k = 1/2 alpha_t (1 - e^-h) / r0.  ``step_coefficients(i)``
+    gives the DDIM 4-tuple (bit for bit DDIMSchedule's), k (float64) and the order: 1 at the first step, at the last one when
+    there are fewer than 15 steps (lower_order_final) and everywhere with solver_order=1 (then the loop is the DDIM loop)."""
+
+    def __init__(self, solver_order=2, lower_order_final=True):
+        if solver_order not in (1, 2):
+            raise ValueError("DPMSolverSchedule: solver_order must be 1 or 2, got %r" % (solver_order,))
+        self.solver_order, self.lower_order_final = solver_order, bool(lower_order_final)
+        self.ddim = DDIMSchedule()
+        self.alphas_cumprod, self.final_alpha_cumprod = self.ddim.alphas_cumprod, self.ddim.final_alpha_cumprod
+        self.num_train_timesteps = self.ddim.num_train_timesteps
+
+    def set_timesteps(self, n):
+        self.timesteps = self.ddim.set_timesteps(n)
+        self.num_inference_steps = n
+        return self.timesteps
+
+    def alpha_sigma(self, t):
+        """(alpha, sigma) of timestep t in float64; t < 0 is the final target alphas_cumprod[0]."""
+        a = float(self.alphas_cumprod[t] if t >= 0 else self.final_alpha_cumprod)
+        return math.sqrt(a), math.sqrt(1.0 - a)
+
+    def lam(self, t):
+        a, s = self.alpha_sigma(t)
+        return math.log(a) - math.log(s)
+
+    def prev(self, t):
+        return t - self.num_train_timesteps // self.num_inference_steps
+
+    def order(self, i):
+        n = len(self.timesteps)
+        if self.solver_order == 1 or i == 0 or (self.lower_order_final and i == n - 1 and n < 15):
+            return 1
+        return 2
+
+    def step_coefficients(self, i):
+        """(DDIM 4-tuple, k, order) of step index i; k = 0.0 at a first-order step."""
+        s0 = self.timesteps[i]
+        coef = self.ddim.coefficients(s0)
+        order = self.order(i)
+        if order == 1:
+            return coef, 0.0, 1
+        t, s1 = self.prev(s0), self.timesteps[i - 1]
+        lam_t, lam_s0, lam_s1 = self.lam(t), self.lam(s0), self.lam(s1)
+        h = lam_t - lam_s0
+        r0 = (lam_s0 - lam_s1) / h
+        k = 0.5 * self.alpha_sigma(t)[0] * -math.expm1(-h) / r0
+        return coef, k, 2
+
+
+def _make_sampler(sampler):
+    """DenoiseLoop's ``sampler`` argument -> None (DDIM) or a private DPMSolverSchedule."""
+    if isinstance(sampler, DPMSolverSchedule):
+        return copy.deepcopy(sampler)                   # set_timesteps below must not touch the caller's object
+    if isinstance(sampler, str) and sampler == "ddim":
+        return None
+    if isinstance(sampler, str) and sampler == "dpmpp_2m":
+        return DPMSolverSchedule()
+    raise ValueError("sampler must be 'ddim', 'dpmpp_2m' or a DPMSolverSchedule, got %r" % (sampler,))
+
+
 def init_noise(pano_noise, cameras, pers_h, pers_w):
     """View noise = nearest-neighbour e2p of the SAME panorama noise (PanFusion.py:30-43).
     pano_noise (bs, 1, 4, H, W) on the GPU; cameras: dict of (bs, m)."""
@@ -60,10 +134,11 @@ class DenoiseLoop:
     """One text-to-panorama sampling run (batch 1 prompt, CFG pair inside)."""
 
     def __init__(self, model, latents, pano_latent, prompt_embd, pano_prompt_embd, cameras,
-                 steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None):
+                 steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None, sampler="ddim"):
         """latents (1, m, 4, h, w), pano_latent (1, 1, 4, H, W) fp32 on the GPU;
         prompt_embd (2, m, L, D) / pano_prompt_embd (2, 1, L, D) = [null ; prompt];
-        cameras: dict of (1, m) CPU tensors (FoV, theta, phi in degrees)."""
+        cameras: dict of (1, m) CPU tensors (FoV, theta, phi in degrees);
+        sampler: "ddim" (default), "dpmpp_2m" or a DPMSolverSchedule (changes the outputs by design: DESIGN.md §4.5)."""
         self.model, self.guidance, self.rot_diff = model, guidance_scale, rot_diff
         # The loop's state lives as the CFG PAIR the denoiser reads ([x ; x], gen_cls_free_guide_pair, PanoGenerator.py:240-251):
         # the DDIM kernel writes both halves, so no torch.cat runs between two calls.  self.lat / self.pano are the first halves.
@@ -77,6 +152,13 @@ class DenoiseLoop:
         self.shift = int(rot_diff / 360 * self.W)          # PanoGenerator.py:269
         self.sched = DDIMSchedule()
         self.timesteps = self.sched.set_timesteps(steps)
+        self.solver = _make_sampler(sampler)
+        if self.solver is not None:
+            self.solver.set_timesteps(steps)
+            # the multistep history: x0 of the previous step, one buffer per latent (never shared); the panorama's is kept in the
+            # frame of the next call (the update kernel writes it rolled, as it writes the state)
+            self.x0_lat = torch.empty_like(self.lat)
+            self.x0_pano = torch.empty_like(self.pano)
         self.tstep = torch.empty(2, self.m, dtype=torch.long, device=latents.device)
         self._tstep_value = None                          # what self.tstep holds (the DDIM kernel writes the next step's value)
         self.i = 0
@@ -197,16 +279,29 @@ class DenoiseLoop:
         # Two launches update the whole loop state IN PLACE (captured graphs read it by address): views -- plain update, both
         # halves of the CFG pair; panorama -- update + roll for the next iteration (a block owns whole rows, so in place for any
         # roll), both halves, and the next call's timestep words.
-        ops.cfg_ddim_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:])
         t_next = t if last else self.timesteps[self.i + 1]
-        ops.cfg_ddim_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
-                               out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next)
+        if self.solver is None:
+            ops.cfg_ddim_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:])
+            ops.cfg_ddim_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
+                                   out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next)
+        else:
+            self._dpmpp_update(eps, pano_eps, last, t_next)
         self._tstep_value = t_next
         self.i += 1
         if not last:
             self.cameras = rotate_cameras(self.cameras, self.rot_diff)
             self.total_rot += self.rot_diff
             self._rot_of.setdefault(tuple(float(v) for v in self.cameras["theta"].reshape(-1)), self.total_rot)
+
+    def _dpmpp_update(self, eps, pano_eps, last, t_next):
+        """The same two launches with the 2M correction; each writes its latent's x0 history (the panorama's rolled like the state)."""
+        coef, k, order = self.solver.step_coefficients(self.i)
+        second = order == 2
+        ops.cfg_dpmpp_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
+                                x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat)
+        ops.cfg_dpmpp_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
+                                out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
+                                x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano)
 
     def run(self):
         while self.i < len(self.timesteps):

@@ -1,0 +1,102 @@
+"""DDIM vs DPM-Solver++(2M) on the benchmark configuration (cfg 2: 512x1024 panorama + 20 views of 512^2, CFG pair,
+SD-2-base shapes, hipGraphs, bench.py's model and inputs).
+
+    python tools/sampler_bench.py [--steps 20] [--repeats 2] [--out result.json]
+    python tools/sampler_bench.py --profile          # short runs of both samplers, for rocprofv3 --kernel-trace --stats
+
+Prints one JSON line:
+  * ms_per_step -- the loop step (denoiser graph replay + the two update launches) of each sampler, timed after warm-up
+    like bench.py, the samplers alternated ``--repeats`` times on the same model;
+  * time_to_latents_s -- wall time from the first step to the final (un-rotated) latents of DDIM-50, 2M-25 and 2M-20
+    (prepare(), i.e. tables and graph capture, untimed).
+Fewer steps is what 2M is for; whether 2M-20/25 images match DDIM-50 in quality is NOT measured here (no trained weights).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20, help="timed steps per ms_per_step sample")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"])
+    ap.add_argument("--profile", action="store_true", help="6 steps of each sampler, no timing (run under rocprofv3)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import bench
+    from panfusion_amd.models.sd2_unet_params import SD2_BASE
+    from panfusion_amd.pipeline import DenoiseLoop
+    from panfusion_amd.utils.pano import icosahedron_sample_camera
+
+    dev = torch.device("cuda", 0)
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    cfg = dict(SD2_BASE)
+    th, ph = icosahedron_sample_camera()
+    model = bench.build_model(dev, dtype, cfg)
+    inputs = bench.build_inputs(dev, 20, (64, 64), (64, 128), cfg["cross_attention_dim"], (np.degrees(th), np.degrees(ph)))
+
+    def make(sampler, steps):
+        loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler)
+        loop.prepare()
+        return loop
+
+    if args.profile:
+        for sampler in ("ddim", "dpmpp_2m"):
+            loop = make(sampler, 6)
+            loop.run()
+            torch.cuda.synchronize()
+            del loop
+        print(json.dumps({"profile": "ddim and dpmpp_2m, 6 steps each"}))
+        return
+
+    per_step = {"ddim": [], "dpmpp_2m": []}
+    for _ in range(args.repeats):
+        for sampler in ("ddim", "dpmpp_2m"):
+            loop = make(sampler, args.steps + args.warmup)
+            for _ in range(args.warmup):
+                loop.step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                loop.step()
+            torch.cuda.synchronize()
+            per_step[sampler].append((time.perf_counter() - t0) / args.steps * 1e3)
+            del loop
+            torch.cuda.empty_cache()
+
+    to_latents = {}
+    for name, sampler, steps in (("ddim_50", "ddim", 50), ("dpmpp_2m_25", "dpmpp_2m", 25), ("dpmpp_2m_20", "dpmpp_2m", 20)):
+        loop = make(sampler, steps)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lat, pano = loop.run()
+        torch.cuda.synchronize()
+        to_latents[name] = time.perf_counter() - t0
+        assert bool(torch.isfinite(lat).all()) and bool(torch.isfinite(pano).all()), name
+        del loop, lat, pano
+        torch.cuda.empty_cache()
+
+    res = {"workload": "cfg2: 512x1024 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes, hipGraphs, %s" % args.dtype,
+           "ms_per_step": {k: [round(v, 3) for v in vs] for k, vs in per_step.items()},
+           "time_to_latents_s": {k: round(v, 4) for k, v in to_latents.items()},
+           "note": "image quality at 20 / 25 steps of 2M vs 50 of DDIM: not measured"}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
