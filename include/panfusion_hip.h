@@ -253,6 +253,27 @@ pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eps_uncond, const 
                                  int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
                                  float* x0_out, void* stream);
 
+/* The loop's update with a known region (inpainting / outpainting at strength 1): diffusers StableDiffusionInpaintPipeline
+ * 0.24, the 4-channel branch, in the loop of PanFusion.py:159-162.  After the DDIM update (x0_out == NULL, the operation
+ * sequence of pf_cfg_ddim_step_pair) or the 2M update (x0_out != NULL, that of pf_cfg_dpmpp_step_pair, x0 written as there)
+ * every element is blended with the known latent z:
+ *   v <- fmaf(m, v, (1 - m) * fmaf(ka, z, kb * n)),  (ka, kb) = (sqrt abar(t_next), sqrt(1 - abar(t_next))), (1, 0) at the last step
+ * i.e. m v + (1 - m) add_noise(z, n, t_next); m = 1 generates, m = 0 keeps (diffusers' convention); n = the loop's starting
+ * latents.  m = 1 gives the unblended value and m = 0 with (1, 0) gives z, bit for bit (finite operands).  The x0 history is
+ * the model's x0 of the blended state: the blend does not touch it.
+ * Frames: known / noise / mask stay in the caller's frame and are read at column (w - known_roll) mod W -- the panorama passes
+ * the sum of the integer rolls its state has gone through before this update (PanoGenerator.py:264-269: (i + 1) shift mod W at
+ * step i), the views 0; the blended value is written at (w + roll) mod W as by the other update kernels.
+ * One block per row: out may alias x and x0_out may alias x0_prev for any roll.  DDIM form: one row staged in LDS, W <= 16384,
+ * x0_prev must be NULL; 2M form: two rows, W <= 8192.  known / noise / mask (required, fp32, the shape of x; the host expands a
+ * per-pixel mask over the channels) must not alias out, out2 or x0_out; the other aliasing rules are pf_cfg_dpmpp_step_pair's. */
+pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
+                                   float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
+                                   float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
+                                   int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                   float* x0_out, const float* known, const float* noise, const float* mask,
+                                   float ka, float kb, int known_roll, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MFMA GEMM / implicit-GEMM convolution (replaces cuDNN/cuBLAS behind diffusers Conv2d/Linear:
  * MVGenModel.py:86-144,174-198,224-294 and transformer.py:57-74,8-38).

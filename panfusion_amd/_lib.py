@@ -130,6 +130,10 @@ SIGNATURES = {
     "pf_cfg_dpmpp_step_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
                                        c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, C.c_int64,
                                        c_void_p, c_float, c_void_p, c_void_p]),
+    "pf_cfg_inpaint_step_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
+                                         c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, C.c_int64,
+                                         c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                         c_int, c_void_p]),
     "pf_conv_gemm": (c_int, [C.POINTER(ConvDesc), c_void_p]),
     "pf_conv_gemm_workspace_size": (c_size_t, [C.POINTER(ConvDesc)]),
     "pf_conv_gemm_gn_rows": (c_int, [C.POINTER(ConvDesc)]),

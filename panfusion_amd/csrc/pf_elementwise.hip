@@ -1,6 +1,7 @@
 // HBM-bound kernels of the denoising path for gfx950: GroupNorm statistics / apply(+SiLU),
 // LayerNorm(+positional encoding), GEGLU, timestep features, circular width pad / crop, layout
-// converters, CFG+DDIM / DPM-Solver++(2M) updates, and the two 4-channel boundary convolutions.
+// converters, CFG+DDIM / DPM-Solver++(2M) updates (with or without a known region), and the two 4-channel
+// boundary convolutions.
 //
 // All activations are NHWC 16-bit, moved as 16-byte (8-element) vectors; statistics are fp32
 // (fp64 for the final GroupNorm moments); reductions are wavefront (64-lane) shuffles.
@@ -635,6 +636,53 @@ __global__ __launch_bounds__(256) void k_cfg_dpmpp_rows(const float* x, const fl
         out[base + w] = v;
         if (out2) out2[base + w] = v;
         x0_out[base + w] = row_x0[w];
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
+}
+
+// ---- CFG + DDIM / DPM-Solver++(2M) with a known region (inpainting / outpainting) ------------------------------
+// k_cfg_ddim_rows (X0 = false) / k_cfg_dpmpp_rows (X0 = true) with diffusers' StableDiffusionInpaintPipeline blend after the
+// update: v <- m v + (1 - m) (ka z + kb n).  z / n / m stay in the caller's frame and are read at column (w - known_roll) mod W
+// (known_roll in [0, W)); m = 1 leaves v unchanged, m = 0 with (ka, kb) = (1, 0) gives z, bit for bit (finite operands).
+__device__ __forceinline__ float known_blend(float v, float m, float z, float n, float ka, float kb) {
+    return __builtin_fmaf(m, v, (1.0f - m) * __builtin_fmaf(ka, z, kb * n));
+}
+
+template <bool X0>
+__global__ __launch_bounds__(256) void k_cfg_inpaint_rows(const float* x, const float* __restrict__ eu,
+                                                          const float* __restrict__ ec, float g, float sa, float sb, float sap,
+                                                          float sbp, const float* x0_prev, float k, const float* __restrict__ known,
+                                                          const float* __restrict__ noise, const float* __restrict__ mask,
+                                                          float ka, float kb, int known_roll, int W, int roll, float* out,
+                                                          float* out2, float* x0_out, long long* tstep, int n_tstep,
+                                                          long long t_next) {
+    extern __shared__ float stage[];
+    float* row = stage;
+    float* row_x0 = stage + W;
+    const long base = static_cast<long>(blockIdx.x) * W;
+    for (int w = threadIdx.x; w < W; w += 256) {
+        int wo = w + roll;
+        wo -= wo >= W ? W : 0;
+        int wk = w - known_roll;
+        wk += wk < 0 ? W : 0;
+        float v;
+        if (X0) {
+            float x0;
+            v = cfg_ddim_value_x0(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp, x0);
+            if (x0_prev) v = __builtin_fmaf(k, x0 - x0_prev[base + w], v);
+            row_x0[wo] = x0;
+        } else {
+            v = cfg_ddim_value(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp);
+        }
+        row[wo] = known_blend(v, mask[base + wk], known[base + wk], noise[base + wk], ka, kb);
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+        if (X0) x0_out[base + w] = row_x0[w];
     }
     if (tstep && blockIdx.x == 0)
         for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
@@ -1397,6 +1445,44 @@ extern "C" pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eu, con
                        as_stream(stream), x, eu, ec, g, sa, sb, sap, sbp, x0_prev, k, W, r, out, out2, x0_out,
                        reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
     PF_CHECK_LAUNCH("pf_cfg_dpmpp_step_pair");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb,
+                                              float sap, float sbp, long rows, int W, int roll, float* out, float* out2,
+                                              int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                              float* x0_out, const float* known, const float* noise, const float* mask,
+                                              float ka, float kb, int known_roll, void* stream) {
+    PF_REQUIRE(x && eu && ec && out && known && noise && mask && rows > 0 && W > 0,
+               "pf_cfg_inpaint_step_pair: bad arguments (known, noise and mask are required)");
+    PF_REQUIRE(x0_out || !x0_prev, "pf_cfg_inpaint_step_pair: x0_prev requires x0_out (x0_out == NULL is the DDIM form)");
+    const int max_w = x0_out ? 8192 : 16384;
+    PF_REQUIRE(rows < (1L << 31) && W <= max_w,
+               "pf_cfg_inpaint_step_pair: rows=%ld must be < 2^31 and W=%d <= %d (one row per block, %s staged in LDS)", rows, W,
+               max_w, x0_out ? "two rows" : "one row");
+    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_inpaint_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
+    PF_REQUIRE(!x0_out || (x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2),
+               "pf_cfg_inpaint_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
+    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_inpaint_step_pair: x0_prev must not alias out / out2");
+    const float* ops_in[3] = {known, noise, mask};
+    for (const float* p : ops_in)
+        PF_REQUIRE(p != out && p != out2 && p != x0_out,
+                   "pf_cfg_inpaint_step_pair: known / noise / mask must not alias out, out2 or x0_out (they are read at an offset)");
+    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_inpaint_step_pair: n_tstep must be positive with tstep");
+    int r = roll % W;
+    if (r < 0) r += W;
+    int kr = known_roll % W;
+    if (kr < 0) kr += W;
+    const size_t lds = (x0_out ? 2 : 1) * static_cast<size_t>(W) * sizeof(float);
+    if (x0_out)
+        hipLaunchKernelGGL(k_cfg_inpaint_rows<true>, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu, ec,
+                           g, sa, sb, sap, sbp, x0_prev, k, known, noise, mask, ka, kb, kr, W, r, out, out2, x0_out,
+                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
+    else
+        hipLaunchKernelGGL(k_cfg_inpaint_rows<false>, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu,
+                           ec, g, sa, sb, sap, sbp, nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, nullptr,
+                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
+    PF_CHECK_LAUNCH("pf_cfg_inpaint_step_pair");
     return PF_OK;
 }
 

@@ -471,6 +471,31 @@ def cfg_dpmpp_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=Non
     return out, x0_out
 
 
+def cfg_inpaint_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0,
+                          x0_prev=None, k=0.0, x0_out=None, *, known, noise, mask, ka, kb, known_roll=0):
+    """cfg_ddim_step_pair (``x0_out=None``) or cfg_dpmpp_step_pair (``x0_out`` given) followed by the known-region blend
+    v <- m v + (1 - m) (ka known + kb noise) (mask 1 = generate, 0 = keep).  ``known`` / ``noise`` / ``mask``
+    (fp32, the shape of x) are read at column (w - known_roll) mod W.  Returns (out, x0_out); x0_out is None in the DDIM form."""
+    W = x.shape[-1]
+    rows = x.numel() // W
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and (out2 is None or out2.is_contiguous())
+    assert x0_out is None or (x0_out.is_contiguous() and x0_out.dtype == torch.float32 and x0_out.numel() == x.numel())
+    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
+    for t in (known, noise, mask):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel())
+    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    sa, sb, sap, sbp = (float(c) for c in coef)
+    opt = lambda t: _p(t) if t is not None else None
+    check(_lib.lib().pf_cfg_inpaint_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
+                                              rows, W, int(roll), _p(out), opt(out2), opt(tstep),
+                                              tstep.numel() if tstep is not None else 0, int(t_next), opt(x0_prev), float(k),
+                                              opt(x0_out), opt(known), opt(noise), opt(mask), float(ka), float(kb),
+                                              int(known_roll), _stream()), "pf_cfg_inpaint_step_pair")
+    return out, x0_out
+
+
 # ---------------------------------------------------------------------------- GEMM / conv
 def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, stride=1, pad=0, upsample=0,
               bias=None, rowvec=None, residual=None, out=None, out_dtype=None, batch=1,

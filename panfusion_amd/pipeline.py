@@ -8,7 +8,9 @@ captured into one hipGraph per rotation offset (the geometry is 4-periodic,
 SURVEY.md §4) and replayed; the CFG+DDIM update is a separate fused kernel
 whose scalar coefficients change every step.  ``sampler="dpmpp_2m"`` swaps the
 update for DPM-Solver++(2M) on the same timestep grid (``DPMSolverSchedule``,
-DESIGN.md §4.5); DDIM stays the default.
+DESIGN.md §4.5); DDIM stays the default.  ``known=KnownRegion(...)`` blends
+known content into the state inside the same two update launches
+(inpainting / outpainting).
 """
 import copy
 import math
@@ -124,6 +126,72 @@ def init_noise(pano_noise, cameras, pers_h, pers_w):
     return pano_noise, noise.unflatten(0, (bs, m))
 
 
+def _keep_mask(gen):
+    """An image-resolution mask (n, 1, 8h, 8w), 1 = generate -> the latent mask (n, 1, h, w): a latent pixel is kept (0) only
+    if all 64 pixels of its 8x8 block are known (mask < 0.5, diffusers' binarisation)."""
+    return torch.nn.functional.max_pool2d((gen >= 0.5).float(), 8)
+
+
+class KnownRegion:
+    """Latent-level known content of an inpainting / outpainting run.
+
+    latents (1, m, 4, h, w) and mask (1, m, 1, h, w) for the views, pano_latent (1, 1, 4, H, W) and pano_mask (1, 1, 1, H, W) for
+    the panorama, all in the caller's (un-rotated) frame.  MASK CONVENTION (diffusers'): 1 = generate, 0 = keep, values in
+    [0, 1].  ``DenoiseLoop(..., known=...)`` checks the shapes against its latents."""
+
+    def __init__(self, latents, mask, pano_latent, pano_mask):
+        self.latents, self.mask, self.pano_latent, self.pano_mask = latents, mask, pano_latent, pano_mask
+
+    @classmethod
+    def from_panorama(cls, vae_encoder, pano, pano_mask, cameras, view_hw, latent_pad=8):
+        """Encode a (partly) known panorama.  pano (1, 1, 3, Hp, Wp) in [-1, 1] and pano_mask (1, 1, 1, Hp, Wp), 1 = generate, on
+        the GPU; cameras: dict of (1, m) (FoV, theta, phi in degrees, as DenoiseLoop takes them); view_hw: the view LATENT size.
+        The panorama latent is the VAE posterior mean x scaling_factor of the circularly padded panorama, unpadded (as the
+        training step encodes it, without the sample draw); the view latents are the means of its bilinear e2p crops at
+        8 view_hw.  A latent pixel is kept only if all 64 pixels of its 8x8 block are known: in pano_mask for the panorama, in
+        each view's nearest e2p crop of pano_mask for that view."""
+        from .utils.pano import pad_pano, unpad_pano
+        if pano.shape[:3] != (1, 1, 3) or pano_mask.shape != (1, 1, 1) + tuple(pano.shape[-2:]):
+            raise ValueError("KnownRegion.from_panorama: pano (1, 1, 3, Hp, Wp) and pano_mask (1, 1, 1, Hp, Wp) expected, got %s, %s"
+                             % (tuple(pano.shape), tuple(pano_mask.shape)))
+        sf = vae_encoder.packed(pano.device).scaling_factor
+        mean, _ = vae_encoder.encode(pad_pano(pano[0].float(), 8 * latent_pad))
+        pano_latent = (unpad_pano(mean, latent_pad) * sf).contiguous()[None]
+        m = cameras["FoV"].shape[1]
+        flat = {k: v.reshape(-1) for k, v in cameras.items()}
+        hw = (8 * view_hw[0], 8 * view_hw[1])
+        crops = e2p(pano[0].float().expand(m, -1, -1, -1), flat["FoV"], flat["theta"], flat["phi"], hw, mode="bilinear")
+        latents = (vae_encoder.encode(crops)[0] * sf)[None]
+        mask_crops = e2p(pano_mask[0].float().expand(m, -1, -1, -1), flat["FoV"], flat["theta"], flat["phi"], hw, mode="nearest")
+        return cls(latents, _keep_mask(mask_crops)[None], pano_latent, _keep_mask(pano_mask[0].float())[None])
+
+    @classmethod
+    def from_view(cls, vae_encoder, image, fov, theta, phi, cameras, pano_hw, view_hw):
+        """Outpaint one photo to 360 degrees: image (1, 3, hi, wi) in [-1, 1] on the GPU, seen with horizontal field of view
+        ``fov`` at (theta, phi) degrees, is projected (p2e) into a panorama of 8 pano_hw pixels, the pixels it does not cover set
+        to 0 and generated (the p2e mask); then from_panorama.  pano_hw / view_hw: the panorama / view LATENT sizes."""
+        from .external.Perspective_and_Equirectangular.p2e import p2e
+        if image.dim() != 4 or image.shape[:2] != (1, 3):
+            raise ValueError("KnownRegion.from_view: image (1, 3, h, w) expected, got %s" % (tuple(image.shape),))
+        equi, covered = p2e(image.float(), [fov], [theta], [phi], (8 * pano_hw[0], 8 * pano_hw[1]))
+        pano = torch.where(covered, equi, torch.zeros((), device=equi.device))
+        return cls.from_panorama(vae_encoder, pano[None], (~covered).float()[None], cameras, view_hw)
+
+    def check(self, latents, pano_latent):
+        """ValueError unless the known content fits the loop's latents (batch 1) and the masks lie in [0, 1]."""
+        lat, pano = tuple(latents.shape), tuple(pano_latent.shape)
+        if lat[0] != 1 or pano[0] != 1:
+            raise ValueError("known content: batch 1 only, the loop's latents are %s / %s" % (lat, pano))
+        want = ((self.latents, lat), (self.mask, lat[:2] + (1,) + lat[3:]), (self.pano_latent, pano),
+                (self.pano_mask, pano[:2] + (1,) + pano[3:]))
+        for name, (t, shape) in zip(("latents", "mask", "pano_latent", "pano_mask"), want):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise ValueError("known content: %s must be %s, got %s" % (name, shape, getattr(t, "shape", type(t))))
+        for name, t in (("mask", self.mask), ("pano_mask", self.pano_mask)):
+            if not bool(((t >= 0) & (t <= 1)).all()):
+                raise ValueError("known content: %s values must lie in [0, 1] (1 = generate, 0 = keep)" % name)
+
+
 def rotate_cameras(cameras, degree):
     cams = dict(cameras)
     cams["theta"] = (cams["theta"] + degree) % 360
@@ -134,11 +202,15 @@ class DenoiseLoop:
     """One text-to-panorama sampling run (batch 1 prompt, CFG pair inside)."""
 
     def __init__(self, model, latents, pano_latent, prompt_embd, pano_prompt_embd, cameras,
-                 steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None, sampler="ddim"):
+                 steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None, sampler="ddim",
+                 known=None):
         """latents (1, m, 4, h, w), pano_latent (1, 1, 4, H, W) fp32 on the GPU;
         prompt_embd (2, m, L, D) / pano_prompt_embd (2, 1, L, D) = [null ; prompt];
         cameras: dict of (1, m) CPU tensors (FoV, theta, phi in degrees);
-        sampler: "ddim" (default), "dpmpp_2m" or a DPMSolverSchedule (changes the outputs by design: DESIGN.md §4.5)."""
+        sampler: "ddim" (default), "dpmpp_2m" or a DPMSolverSchedule (changes the outputs by design: DESIGN.md §4.5);
+        known: a KnownRegion -- inpainting / outpainting at strength 1, the starting latents are the noise."""
+        if known is not None:
+            known.check(latents, pano_latent)
         self.model, self.guidance, self.rot_diff = model, guidance_scale, rot_diff
         # The loop's state lives as the CFG PAIR the denoiser reads ([x ; x], gen_cls_free_guide_pair, PanoGenerator.py:240-251):
         # the DDIM kernel writes both halves, so no torch.cat runs between two calls.  self.lat / self.pano are the first halves.
@@ -159,6 +231,15 @@ class DenoiseLoop:
             # frame of the next call (the update kernel writes it rolled, as it writes the state)
             self.x0_lat = torch.empty_like(self.lat)
             self.x0_pano = torch.empty_like(self.pano)
+        self.known = known
+        if known is not None:
+            # fp32 operands of the blend, all in the caller's frame (the kernel reads the panorama's at the state's offset): the
+            # known latents, the masks expanded over the 4 channels, and the noise n = the starting latents, before the roll below
+            dev = latents.device
+            own = lambda t: t.detach().to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+            self.known_lat, self.known_pano = own(known.latents), own(known.pano_latent)
+            self.mask_lat, self.mask_pano = own(known.mask.expand_as(latents)), own(known.pano_mask.expand_as(pano_latent))
+            self.noise_lat, self.noise_pano = own(latents), own(pano_latent)
         self.tstep = torch.empty(2, self.m, dtype=torch.long, device=latents.device)
         self._tstep_value = None                          # what self.tstep holds (the DDIM kernel writes the next step's value)
         self.i = 0
@@ -280,7 +361,9 @@ class DenoiseLoop:
         # halves of the CFG pair; panorama -- update + roll for the next iteration (a block owns whole rows, so in place for any
         # roll), both halves, and the next call's timestep words.
         t_next = t if last else self.timesteps[self.i + 1]
-        if self.solver is None:
+        if self.known is not None:
+            self._known_update(eps, pano_eps, coef, last, t_next)
+        elif self.solver is None:
             ops.cfg_ddim_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:])
             ops.cfg_ddim_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
                                    out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next)
@@ -302,6 +385,26 @@ class DenoiseLoop:
         ops.cfg_dpmpp_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
                                 out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
                                 x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano)
+
+    def _known_update(self, eps, pano_eps, coef, last, t_next):
+        """The same two launches with the known-region blend after the DDIM or 2M update: x <- m x + (1 - m) r,
+        r = add_noise(known, noise, t_next) = ka known + kb noise, known itself at the last step.  On this grid t_next is the DDIM
+        target of the step, so (ka, kb) are the step's own (sqrt_a_prev, sqrt_1m_a_prev).  The panorama's operands are read at
+        the offset its state has been rolled by before this update: (i + 1) shifts (not total_rot, see result())."""
+        ka, kb = (1.0, 0.0) if last else coef[2:]
+        o = (self.i + 1) * self.shift % self.W
+        blend = lambda z, n, m, roll: dict(known=z, noise=n, mask=m, ka=ka, kb=kb, known_roll=roll)
+        x0 = dict(lat={}, pano={})
+        if self.solver is not None:
+            coef, k, order = self.solver.step_coefficients(self.i)
+            second = order == 2
+            x0 = dict(lat=dict(x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat),
+                      pano=dict(x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano))
+        ops.cfg_inpaint_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
+                                  **x0["lat"], **blend(self.known_lat, self.noise_lat, self.mask_lat, 0))
+        ops.cfg_inpaint_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
+                                  out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
+                                  **x0["pano"], **blend(self.known_pano, self.noise_pano, self.mask_pano, o))
 
     def run(self):
         while self.i < len(self.timesteps):

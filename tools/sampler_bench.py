@@ -3,6 +3,7 @@ SD-2-base shapes, hipGraphs, bench.py's model and inputs).
 
     python tools/sampler_bench.py [--steps 20] [--repeats 2] [--out result.json]
     python tools/sampler_bench.py --profile          # short runs of both samplers, for rocprofv3 --kernel-trace --stats
+    python tools/sampler_bench.py --known [--profile]  # DDIM without / with known content (inpainting)
 
 Prints one JSON line:
   * ms_per_step -- the loop step (denoiser graph replay + the two update launches) of each sampler, timed after warm-up
@@ -10,6 +11,9 @@ Prints one JSON line:
   * time_to_latents_s -- wall time from the first step to the final (un-rotated) latents of DDIM-50, 2M-25 and 2M-20
     (prepare(), i.e. tables and graph capture, untimed).
 Fewer steps is what 2M is for; whether 2M-20/25 images match DDIM-50 in quality is NOT measured here (no trained weights).
+
+With --known: ms_per_step of DDIM without and with a known region (a seeded panorama latent kept on half of the columns, its
+nearest e2p in the views), alternated the same way; --profile then runs 6 steps of each.
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"])
     ap.add_argument("--profile", action="store_true", help="6 steps of each sampler, no timing (run under rocprofv3)")
+    ap.add_argument("--known", action="store_true", help="DDIM without / with known content instead of DDIM / 2M")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -35,7 +40,7 @@ def main():
     import torch
     import bench
     from panfusion_amd.models.sd2_unet_params import SD2_BASE
-    from panfusion_amd.pipeline import DenoiseLoop
+    from panfusion_amd.pipeline import DenoiseLoop, KnownRegion, init_noise
     from panfusion_amd.utils.pano import icosahedron_sample_camera
 
     dev = torch.device("cuda", 0)
@@ -45,23 +50,36 @@ def main():
     model = bench.build_model(dev, dtype, cfg)
     inputs = bench.build_inputs(dev, 20, (64, 64), (64, 128), cfg["cross_attention_dim"], (np.degrees(th), np.degrees(ph)))
 
+    known = None
+    if args.known:
+        g = torch.Generator().manual_seed(5)
+        pano_z = torch.randn(inputs[1].shape, generator=g).to(dev)
+        pano_m = torch.ones(1, 1, 1, *inputs[1].shape[-2:], device=dev)
+        pano_m[..., :inputs[1].shape[-1] // 2] = 0.0
+        cams, (h, w) = inputs[-1], inputs[0].shape[-2:]
+        known = KnownRegion(init_noise(pano_z, cams, h, w)[1], init_noise(pano_m, cams, h, w)[1], pano_z, pano_m)
+
     def make(sampler, steps):
-        loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler)
+        kn = None
+        if sampler == "ddim_known":
+            sampler, kn = "ddim", known
+        loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler, known=kn)
         loop.prepare()
         return loop
 
+    samplers = ("ddim", "ddim_known") if args.known else ("ddim", "dpmpp_2m")
     if args.profile:
-        for sampler in ("ddim", "dpmpp_2m"):
+        for sampler in samplers:
             loop = make(sampler, 6)
             loop.run()
             torch.cuda.synchronize()
             del loop
-        print(json.dumps({"profile": "ddim and dpmpp_2m, 6 steps each"}))
+        print(json.dumps({"profile": "%s, 6 steps each" % " and ".join(samplers)}))
         return
 
-    per_step = {"ddim": [], "dpmpp_2m": []}
+    per_step = {s: [] for s in samplers}
     for _ in range(args.repeats):
-        for sampler in ("ddim", "dpmpp_2m"):
+        for sampler in samplers:
             loop = make(sampler, args.steps + args.warmup)
             for _ in range(args.warmup):
                 loop.step()
@@ -75,7 +93,8 @@ def main():
             torch.cuda.empty_cache()
 
     to_latents = {}
-    for name, sampler, steps in (("ddim_50", "ddim", 50), ("dpmpp_2m_25", "dpmpp_2m", 25), ("dpmpp_2m_20", "dpmpp_2m", 20)):
+    runs = (("ddim_50", "ddim", 50), ("dpmpp_2m_25", "dpmpp_2m", 25), ("dpmpp_2m_20", "dpmpp_2m", 20))
+    for name, sampler, steps in (() if args.known else runs):
         loop = make(sampler, steps)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
