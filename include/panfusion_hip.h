@@ -274,6 +274,19 @@ pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eps_uncond, cons
                                    float* x0_out, const float* known, const float* noise, const float* mask,
                                    float ka, float kb, int known_roll, void* stream);
 
+/* The start state of a sampling run in ONE launch (PanFusion.py:30-43,146-149: the noise the loop starts from, its first roll
+ * and timestep tensor; PanoGenerator.py:240-251,264-269: the CFG pair [x ; x] and the integer roll), for a start below
+ * strength 1 (diffusers' img2img / inpaint pipelines: latents = scheduler.add_noise(image_latents, noise, latent_timestep)) and
+ * for re-arming a loop whose captured graphs read the state by address:
+ *   out[r][(w + roll) mod W] = fmaf(ka, z[r][w], kb * noise[r][w]),  (ka, kb) = (sqrt abar(t_s), sqrt(1 - abar(t_s)))
+ * -- the expression pf_cfg_inpaint_step_pair uses for its blend operand, so a kept pixel starts on the value the blend would
+ * write -- and the same value to out2 (or NULL), the other half of the CFG pair.  z == NULL: out = noise rolled, a bit-exact
+ * copy (ka, kb unused).  tstep (or NULL): n_tstep int64 words set to t0, the timestep tensor of the first call.
+ * One block per row, the row staged in LDS: W <= 16384.  z / noise fp32, rows x W; out / out2 must not alias z, noise or each
+ * other. */
+pf_status pf_noised_start_pair(const float* z, const float* noise, float ka, float kb, long rows, int W, int roll,
+                               float* out, float* out2, int64_t* tstep, int n_tstep, int64_t t0, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MFMA GEMM / implicit-GEMM convolution (replaces cuDNN/cuBLAS behind diffusers Conv2d/Linear:
  * MVGenModel.py:86-144,174-198,224-294 and transformer.py:57-74,8-38).

@@ -688,6 +688,33 @@ __global__ __launch_bounds__(256) void k_cfg_inpaint_rows(const float* x, const 
         for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
 }
 
+// ---- start state of a run (strength < 1 starts and DenoiseLoop.restart) ----------------------------------------
+// out[(w + roll) mod W] = add_noise(z, n, t_s) = fmaf(ka, z, kb * n) -- known_blend's r, so a kept pixel of a known loop starts on
+// the value the blend would write -- or n itself (z == NULL, a bit-exact rolled copy), to both halves of the CFG pair, plus the
+// first call's timestep words: k_cfg_ddim_rows' staging (one block per row, the row leaves LDS in order), written into buffers
+// that live graphs read.  Latency-bound (1.4 MB at cfg 2): no bandwidth tuning.
+__global__ __launch_bounds__(256) void k_noised_start_rows(const float* __restrict__ z, const float* __restrict__ noise,
+                                                           float ka, float kb, int W, int roll, float* __restrict__ out,
+                                                           float* __restrict__ out2, long long* tstep, int n_tstep,
+                                                           long long t0) {
+    extern __shared__ float row[];
+    const long base = static_cast<long>(blockIdx.x) * W;
+    for (int w = threadIdx.x; w < W; w += 256) {
+        int wo = w + roll;
+        wo -= wo >= W ? W : 0;
+        const float n = noise[base + w];
+        row[wo] = z ? __builtin_fmaf(ka, z[base + w], kb * n) : n;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t0;
+}
+
 // ---- token + position embedding gather (CLIP text encoder, transformers CLIPTextEmbeddings) -------------
 // out[b][t][:] = tok[ids[b][t]][:] + pos[t][:] for t < L, zeros for the padding rows L <= t < Lp.
 template <typename SO>
@@ -1483,6 +1510,23 @@ extern "C" pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eu, c
                            ec, g, sa, sb, sap, sbp, nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, nullptr,
                            reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
     PF_CHECK_LAUNCH("pf_cfg_inpaint_step_pair");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_noised_start_pair(const float* z, const float* noise, float ka, float kb, long rows, int W, int roll,
+                                          float* out, float* out2, int64_t* tstep, int n_tstep, int64_t t0, void* stream) {
+    PF_REQUIRE(noise && out && rows > 0 && W > 0, "pf_noised_start_pair: bad arguments (noise and out are required)");
+    PF_REQUIRE(rows < (1L << 31) && W <= 16384, "pf_noised_start_pair: rows=%ld must be < 2^31 and W=%d <= 16384 (one row per block, staged in LDS)", rows, W);
+    PF_REQUIRE(out2 != out, "pf_noised_start_pair: out2 must be a buffer of its own");
+    PF_REQUIRE(out != noise && out2 != noise && (!z || (out != z && out2 != z)),
+               "pf_noised_start_pair: out / out2 must not alias z or noise (__restrict__ operands)");
+    PF_REQUIRE(!tstep || n_tstep > 0, "pf_noised_start_pair: n_tstep must be positive with tstep");
+    int r = roll % W;
+    if (r < 0) r += W;
+    hipLaunchKernelGGL(k_noised_start_rows, dim3(static_cast<unsigned>(rows)), dim3(256), static_cast<size_t>(W) * sizeof(float),
+                       as_stream(stream), z, noise, ka, kb, W, r, out, out2, reinterpret_cast<long long*>(tstep), n_tstep,
+                       static_cast<long long>(t0));
+    PF_CHECK_LAUNCH("pf_noised_start_pair");
     return PF_OK;
 }
 

@@ -496,6 +496,22 @@ def cfg_inpaint_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=N
     return out, x0_out
 
 
+def noised_start_pair(z, noise, ka, kb, roll=0, *, out, out2=None, tstep=None, t0=0):
+    """The start state of a run in one launch: ``out`` <- ka z + kb noise rolled by ``roll`` along the width
+    (``z=None``: the noise itself, a bit-exact rolled copy), ``out2`` a second copy (the CFG pair's other half), ``tstep`` (int64
+    device tensor) set to ``t0``.  ``out`` / ``out2`` are existing buffers (captured graphs read them) and alias no input."""
+    W = noise.shape[-1]
+    rows = noise.numel() // W
+    for t in (z, noise, out, out2):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == noise.numel())
+    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    opt = lambda t: _p(t) if t is not None else None
+    check(_lib.lib().pf_noised_start_pair(opt(z), _p(noise), float(ka), float(kb), rows, W, int(roll), _p(out), opt(out2),
+                                          opt(tstep), tstep.numel() if tstep is not None else 0, int(t0), _stream()),
+          "pf_noised_start_pair")
+    return out
+
+
 # ---------------------------------------------------------------------------- GEMM / conv
 def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, stride=1, pad=0, upsample=0,
               bias=None, rowvec=None, residual=None, out=None, out_dtype=None, batch=1,

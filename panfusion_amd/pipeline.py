@@ -10,7 +10,10 @@ whose scalar coefficients change every step.  ``sampler="dpmpp_2m"`` swaps the
 update for DPM-Solver++(2M) on the same timestep grid (``DPMSolverSchedule``,
 DESIGN.md §4.5); DDIM stays the default.  ``known=KnownRegion(...)`` blends
 known content into the state inside the same two update launches
-(inpainting / outpainting).
+(inpainting / outpainting).  ``strength=s, init=SourceLatents(...)``
+starts from a noised source and runs the last ``int(steps * s)`` steps of the grid
+(image-to-panorama, partial-strength inpainting), and ``restart()`` re-arms a loop
+in place -- same buffers, same captured graphs -- for the next run.
 """
 import copy
 import math
@@ -83,17 +86,19 @@ class DPMSolverSchedule:
     def prev(self, t):
         return t - self.num_train_timesteps // self.num_inference_steps
 
-    def order(self, i):
+    def order(self, i, first=False):
         n = len(self.timesteps)
-        if self.solver_order == 1 or i == 0 or (self.lower_order_final and i == n - 1 and n < 15):
+        if self.solver_order == 1 or i == 0 or first or (self.lower_order_final and i == n - 1 and n < 15):
             return 1
         return 2
 
-    def step_coefficients(self, i):
-        """(DDIM 4-tuple, k, order) of step index i; k = 0.0 at a first-order step."""
+    def step_coefficients(self, i, first=False):
+        """(DDIM 4-tuple, k, order) of step index i; k = 0.0 at a first-order step.  ``first``: i is the first step a run
+        executes (a strength < 1 start): no history yet, so first order whatever i is (diffusers'
+        lower_order_nums < 1); lower_order_final keeps looking at the full grid."""
         s0 = self.timesteps[i]
         coef = self.ddim.coefficients(s0)
-        order = self.order(i)
+        order = self.order(i, first)
         if order == 1:
             return coef, 0.0, 1
         t, s1 = self.prev(s0), self.timesteps[i - 1]
@@ -132,6 +137,66 @@ def _keep_mask(gen):
     return torch.nn.functional.max_pool2d((gen >= 0.5).float(), 8)
 
 
+def _encode_panorama(vae_encoder, pano, cameras, view_hw, latent_pad=8):
+    """(view latents (1, m, 4, h, w), panorama latent (1, 1, 4, H, W)) of a panorama (1, 1, 3, Hp, Wp) in [-1, 1]: the VAE
+    posterior mean x scaling_factor of the circularly padded panorama, unpadded (as the training step encodes it, without the
+    sample draw), and the means of its bilinear e2p crops at 8 view_hw."""
+    from .utils.pano import pad_pano, unpad_pano
+    sf = vae_encoder.packed(pano.device).scaling_factor
+    mean, _ = vae_encoder.encode(pad_pano(pano[0].float(), 8 * latent_pad))
+    pano_latent = (unpad_pano(mean, latent_pad) * sf).contiguous()[None]
+    m = cameras["FoV"].shape[1]
+    flat = {k: v.reshape(-1) for k, v in cameras.items()}
+    hw = (8 * view_hw[0], 8 * view_hw[1])
+    crops = e2p(pano[0].float().expand(m, -1, -1, -1), flat["FoV"], flat["theta"], flat["phi"], hw, mode="bilinear")
+    latents = (vae_encoder.encode(crops)[0] * sf)[None]
+    return latents, pano_latent
+
+
+def _check_shapes(what, named, batch):
+    """ValueError unless the loop's latents have batch 1 and every (name, tensor, shape) of ``named`` fits."""
+    lat, pano = batch
+    if lat[0] != 1 or pano[0] != 1:
+        raise ValueError("%s: batch 1 only, the loop's latents are %s / %s" % (what, lat, pano))
+    for name, t, shape in named:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, getattr(t, "shape", type(t))))
+
+
+class SourceLatents:
+    """The clean source latents z of a strength < 1 run: latents (1, m, 4, h, w) for the views and pano_latent
+    (1, 1, 4, H, W) for the panorama, in the caller's (un-rotated) frame.  ``DenoiseLoop(..., strength=s, init=...)`` starts
+    from add_noise(z, noise, t_s) and checks the shapes against its latents."""
+
+    def __init__(self, latents, pano_latent):
+        self.latents, self.pano_latent = latents, pano_latent
+
+    @classmethod
+    def from_panorama(cls, vae_encoder, pano, cameras, view_hw, latent_pad=8):
+        """Encode a panorama (1, 1, 3, Hp, Wp) in [-1, 1] on the GPU exactly as KnownRegion.from_panorama does; cameras: dict of
+        (1, m) (FoV, theta, phi in degrees, as DenoiseLoop takes them); view_hw: the view LATENT size."""
+        if pano.dim() != 5 or pano.shape[:3] != (1, 1, 3):
+            raise ValueError("SourceLatents.from_panorama: pano (1, 1, 3, Hp, Wp) expected, got %s" % (tuple(pano.shape),))
+        return cls(*_encode_panorama(vae_encoder, pano, cameras, view_hw, latent_pad))
+
+    def check(self, latents, pano_latent):
+        """ValueError unless the source fits the loop's latents (batch 1)."""
+        lat, pano = tuple(latents.shape), tuple(pano_latent.shape)
+        _check_shapes("source latents", (("latents", self.latents, lat), ("pano_latent", self.pano_latent, pano)), (lat, pano))
+
+
+def executed_steps(steps, strength):
+    """(k, i0) of a strength-s run on a grid of ``steps``: k = min(int(steps * s), steps) executed steps starting at grid index
+    i0 = steps - k (get_timesteps of diffusers' img2img / inpaint pipelines, Python's int() of the float product exactly).
+    ValueError for a strength outside (0, 1], NaN, or one that leaves no step."""
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0 < strength <= 1:
+        raise ValueError("strength must be a number in (0, 1], got %r" % (strength,))
+    k = min(int(steps * strength), steps)
+    if k == 0:
+        raise ValueError("strength %r leaves no step to run on a grid of %d (int(steps * strength) == 0)" % (strength, steps))
+    return k, steps - k
+
+
 class KnownRegion:
     """Latent-level known content of an inpainting / outpainting run.
 
@@ -150,18 +215,13 @@ class KnownRegion:
         training step encodes it, without the sample draw); the view latents are the means of its bilinear e2p crops at
         8 view_hw.  A latent pixel is kept only if all 64 pixels of its 8x8 block are known: in pano_mask for the panorama, in
         each view's nearest e2p crop of pano_mask for that view."""
-        from .utils.pano import pad_pano, unpad_pano
         if pano.shape[:3] != (1, 1, 3) or pano_mask.shape != (1, 1, 1) + tuple(pano.shape[-2:]):
             raise ValueError("KnownRegion.from_panorama: pano (1, 1, 3, Hp, Wp) and pano_mask (1, 1, 1, Hp, Wp) expected, got %s, %s"
                              % (tuple(pano.shape), tuple(pano_mask.shape)))
-        sf = vae_encoder.packed(pano.device).scaling_factor
-        mean, _ = vae_encoder.encode(pad_pano(pano[0].float(), 8 * latent_pad))
-        pano_latent = (unpad_pano(mean, latent_pad) * sf).contiguous()[None]
+        latents, pano_latent = _encode_panorama(vae_encoder, pano, cameras, view_hw, latent_pad)
         m = cameras["FoV"].shape[1]
         flat = {k: v.reshape(-1) for k, v in cameras.items()}
         hw = (8 * view_hw[0], 8 * view_hw[1])
-        crops = e2p(pano[0].float().expand(m, -1, -1, -1), flat["FoV"], flat["theta"], flat["phi"], hw, mode="bilinear")
-        latents = (vae_encoder.encode(crops)[0] * sf)[None]
         mask_crops = e2p(pano_mask[0].float().expand(m, -1, -1, -1), flat["FoV"], flat["theta"], flat["phi"], hw, mode="nearest")
         return cls(latents, _keep_mask(mask_crops)[None], pano_latent, _keep_mask(pano_mask[0].float())[None])
 
@@ -199,51 +259,69 @@ def rotate_cameras(cameras, degree):
 
 
 class DenoiseLoop:
-    """One text-to-panorama sampling run (batch 1 prompt, CFG pair inside)."""
+    """One sampling run (batch 1 prompt, CFG pair inside): text-to-panorama from noise, with ``known`` content kept
+    (inpainting / outpainting), and / or from a noised source at ``strength`` < 1 (``init``); ``restart()`` re-arms it in
+    place for the next run."""
 
     def __init__(self, model, latents, pano_latent, prompt_embd, pano_prompt_embd, cameras,
                  steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None, sampler="ddim",
-                 known=None):
-        """latents (1, m, 4, h, w), pano_latent (1, 1, 4, H, W) fp32 on the GPU;
+                 known=None, strength=1.0, init=None):
+        """latents (1, m, 4, h, w), pano_latent (1, 1, 4, H, W) fp32 on the GPU: the NOISE (init_noise);
         prompt_embd (2, m, L, D) / pano_prompt_embd (2, 1, L, D) = [null ; prompt];
         cameras: dict of (1, m) CPU tensors (FoV, theta, phi in degrees);
         sampler: "ddim" (default), "dpmpp_2m" or a DPMSolverSchedule (changes the outputs by design: DESIGN.md §4.5);
-        known: a KnownRegion -- inpainting / outpainting at strength 1, the starting latents are the noise."""
+        known: a KnownRegion -- inpainting / outpainting (DESIGN.md §4.6);
+        strength in (0, 1], init: a SourceLatents -- the run starts from add_noise(init, noise, t_s) and executes the last
+        int(steps * strength) steps of the grid; init defaults to the known latents.  At strength 1 the start
+        is the noise itself, with or without init."""
+        k, i0 = executed_steps(steps, strength)
         if known is not None:
             known.check(latents, pano_latent)
+        if init is not None:
+            init.check(latents, pano_latent)
+        if k < steps:
+            if init is None and known is None:
+                raise ValueError("strength %r < 1 needs source latents: init=SourceLatents(...) or known=KnownRegion(...)" % (strength,))
+            if latents.shape[0] != 1 or pano_latent.shape[0] != 1:
+                raise ValueError("strength < 1: batch 1 only, the loop's latents are %s / %s"
+                                 % (tuple(latents.shape), tuple(pano_latent.shape)))
         self.model, self.guidance, self.rot_diff = model, guidance_scale, rot_diff
-        # The loop's state lives as the CFG PAIR the denoiser reads ([x ; x], gen_cls_free_guide_pair, PanoGenerator.py:240-251):
-        # the DDIM kernel writes both halves, so no torch.cat runs between two calls.  self.lat / self.pano are the first halves.
-        self.lat2 = torch.stack([latents.float()[0]] * 2).contiguous()
-        self.pano2 = torch.stack([pano_latent.float()[0]] * 2).contiguous()
-        self.lat, self.pano = self.lat2[:1], self.pano2[:1]
         self.prompt, self.pano_prompt = prompt_embd, pano_prompt_embd
-        self.cameras = {k: v.detach().cpu() for k, v in cameras.items()}
+        self._cameras0 = {k_: v.detach().cpu() for k_, v in cameras.items()}
         self.m = latents.shape[1]
         self.W = pano_latent.shape[-1]
         self.shift = int(rot_diff / 360 * self.W)          # PanoGenerator.py:269
         self.sched = DDIMSchedule()
-        self.timesteps = self.sched.set_timesteps(steps)
+        self.steps = steps
+        self._grid = self.sched.set_timesteps(steps)
+        self.strength, self.i0 = strength, i0
+        self.timesteps = self._grid[i0:]                   # the executed steps (all of the grid at strength 1)
         self.solver = _make_sampler(sampler)
-        if self.solver is not None:
-            self.solver.set_timesteps(steps)
-            # the multistep history: x0 of the previous step, one buffer per latent (never shared); the panorama's is kept in the
-            # frame of the next call (the update kernel writes it rolled, as it writes the state)
-            self.x0_lat = torch.empty_like(self.lat)
-            self.x0_pano = torch.empty_like(self.pano)
+        dev = latents.device
+        own = lambda t: t.detach().to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+        # The loop's state lives as the CFG PAIR the denoiser reads ([x ; x], gen_cls_free_guide_pair, PanoGenerator.py:240-251):
+        # the DDIM kernel writes both halves, so no torch.cat runs between two calls.  self.lat / self.pano are the first halves.
+        if k == steps:
+            self.lat2 = torch.stack([latents.float()[0]] * 2).contiguous()
+            self.pano2 = torch.stack([pano_latent.float()[0]] * 2).contiguous()
+        else:                                              # filled by _write_start below
+            self.lat2 = torch.empty((2,) + tuple(latents.shape[1:]), dtype=torch.float32, device=dev)
+            self.pano2 = torch.empty((2,) + tuple(pano_latent.shape[1:]), dtype=torch.float32, device=dev)
         self.known = known
         if known is not None:
             # fp32 operands of the blend, all in the caller's frame (the kernel reads the panorama's at the state's offset): the
-            # known latents, the masks expanded over the 4 channels, and the noise n = the starting latents, before the roll below
-            dev = latents.device
-            own = lambda t: t.detach().to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+            # known latents, the masks expanded over the 4 channels, and the noise n, before the first roll
             self.known_lat, self.known_pano = own(known.latents), own(known.pano_latent)
             self.mask_lat, self.mask_pano = own(known.mask.expand_as(latents)), own(known.pano_mask.expand_as(pano_latent))
-            self.noise_lat, self.noise_pano = own(latents), own(pano_latent)
-        self.tstep = torch.empty(2, self.m, dtype=torch.long, device=latents.device)
-        self._tstep_value = None                          # what self.tstep holds (the DDIM kernel writes the next step's value)
-        self.i = 0
-        self.total_rot = 0.0
+        # the noise operand: the loop's own copy where a kernel reads it after construction (the blend; restart() copies new
+        # noise into it), the caller's tensors otherwise until a restart() needs them
+        self._owns_noise = known is not None or k < steps
+        self.noise_lat, self.noise_pano = (own(latents), own(pano_latent)) if self._owns_noise else (latents, pano_latent)
+        # the source z of a strength < 1 start: the loop's own copy of init, else the known latents themselves
+        self.src_lat = self.src_pano = None
+        if init is not None:
+            self.src_lat, self.src_pano = own(init.latents), own(init.pano_latent)
+        self.tstep = torch.empty(2, self.m, dtype=torch.long, device=dev)
         self.use_graphs = use_graphs
         self.graphs = {}
         # layout condition image (1, 1, 3, Hi, Wi) for the panorama ControlNet: rolled with the panorama
@@ -251,14 +329,94 @@ class DenoiseLoop:
         self.layout = None if pano_layout_cond is None else pano_layout_cond.float().contiguous()
         self._layout_rot = {}
         self.eps = self.pano_eps = None
-        # the loop rolls the panorama BEFORE each denoiser call (PanFusion.py:149); afterwards the
-        # DDIM kernel writes the next latent already rolled for the following step.
         self._rot_of = {}                                  # camera-theta key -> accumulated rotation (degrees)
-        if rot_diff % 360:
-            self.pano2.copy_(ops.roll_width(self.pano2, self.shift))       # (one-off set-up, not part of a step)
-        self.cameras = rotate_cameras(self.cameras, rot_diff)
-        self.total_rot += rot_diff
-        self._rot_of[tuple(float(v) for v in self.cameras["theta"].reshape(-1))] = self.total_rot
+        self.lat, self.pano = self.lat2[:1], self.pano2[:1]
+        if self.solver is not None:
+            self.solver.set_timesteps(steps)
+            # the multistep history: x0 of the previous step, one buffer per latent (never shared); the panorama's is kept in the
+            # frame of the next call (the update kernel writes it rolled, as it writes the state)
+            self.x0_lat = torch.empty_like(self.lat)
+            self.x0_pano = torch.empty_like(self.pano)
+        # The loop rolls the panorama BEFORE each denoiser call (PanFusion.py:149); afterwards the DDIM kernel writes the next
+        # latent already rolled for the following step.
+        if k == steps:
+            if rot_diff % 360:
+                self.pano2.copy_(ops.roll_width(self.pano2, self.shift))       # (one-off set-up, not part of a step)
+            self._tstep_value = None                      # what self.tstep holds (the DDIM kernel writes the next step's value)
+        else:
+            self._write_start()
+        self._rewind()
+
+    def _rewind(self):
+        """Counters and cameras of "constructed, before the first step": the state has been rolled once."""
+        self.i = 0                                         # EXECUTED steps so far; the grid index of a step is i0 + i
+        self.cameras = rotate_cameras(self._cameras0, self.rot_diff)
+        self.total_rot = 0.0 + self.rot_diff
+        self._rot_of.setdefault(tuple(float(v) for v in self.cameras["theta"].reshape(-1)), self.total_rot)
+
+    def _write_start(self):
+        """The start state, both halves of the pair, rolled for the first call, and the first call's timestep words, written IN
+        PLACE by two launches (captured graphs read these buffers): add_noise(z, n, t_s) below strength 1, n itself at 1."""
+        t0 = self.timesteps[0]
+        ka = kb = 0.0
+        z_lat = z_pano = None
+        if self.i0 > 0:
+            ka, kb = self.sched.coefficients(t0)[:2]
+            z_lat, z_pano = (self.known_lat, self.known_pano) if self.src_lat is None else (self.src_lat, self.src_pano)
+        roll = self.shift if self.rot_diff % 360 else 0
+        ops.noised_start_pair(z_lat, self.noise_lat, ka, kb, 0, out=self.lat, out2=self.lat2[1:])
+        ops.noised_start_pair(z_pano, self.noise_pano, ka, kb, roll, out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t0=t0)
+        self._tstep_value = t0
+
+    def restart(self, latents=None, pano_latent=None, *, strength=None, init=None, known=None):
+        """Back to "constructed, before the first step" IN PLACE: state pair, timestep words, step counters, cameras, total_rot,
+        the 2M order; and -- where given -- new noise, a new source, new known contents (same shapes, copied into the loop's own
+        operand buffers) and a new strength.  None keeps the current value.  Captured graphs, EPA tables and pinned text K/V stay
+        valid: no buffer a graph reads is allocated and no address changes.  Not re-armable: steps, sampler, rot_diff, guidance,
+        prompts, cameras, and whether the loop has known content at all."""
+        shape_lat, shape_pano = (1,) + tuple(self.lat.shape[1:]), (1,) + tuple(self.pano.shape[1:])
+        like_lat, like_pano = torch.empty(shape_lat, device="meta"), torch.empty(shape_pano, device="meta")
+        _check_shapes("restart", [(n, t, s) for n, t, s in (("latents", latents, shape_lat), ("pano_latent", pano_latent, shape_pano))
+                                  if t is not None], (shape_lat, shape_pano))
+        if known is not None:
+            if self.known is None:
+                raise ValueError("restart: this loop was built without known content (known= cannot be added by a restart)")
+            known.check(like_lat, like_pano)
+        if init is not None:
+            init.check(like_lat, like_pano)
+        new_strength = self.strength if strength is None else strength
+        k, i0 = executed_steps(self.steps, new_strength)
+        if k < self.steps and init is None and self.src_lat is None and self.known is None:
+            raise ValueError("restart: strength %r < 1 needs source latents: init=SourceLatents(...)" % (new_strength,))
+        # everything is valid: from here on the loop changes
+        dev = self.lat.device
+        put = lambda buf, t: buf.copy_(t.detach().to(dev, torch.float32))
+        if not self._owns_noise:
+            # a loop built with defaults kept the caller's noise tensors: it takes its own copies now (operands of the start
+            # kernel only; no graph reads them)
+            own = lambda t: t.detach().to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+            self.noise_lat = own(self.noise_lat if latents is None else latents)
+            self.noise_pano = own(self.noise_pano if pano_latent is None else pano_latent)
+            self._owns_noise, latents, pano_latent = True, None, None
+        if latents is not None:
+            put(self.noise_lat, latents)
+        if pano_latent is not None:
+            put(self.noise_pano, pano_latent)
+        if known is not None:
+            self.known = known
+            put(self.known_lat, known.latents)
+            put(self.known_pano, known.pano_latent)
+            put(self.mask_lat, known.mask.expand_as(self.mask_lat))
+            put(self.mask_pano, known.pano_mask.expand_as(self.mask_pano))
+        if init is not None:
+            if self.src_lat is None:
+                self.src_lat, self.src_pano = torch.empty_like(self.noise_lat), torch.empty_like(self.noise_pano)
+            put(self.src_lat, init.latents)
+            put(self.src_pano, init.pano_latent)
+        self.strength, self.i0 = new_strength, i0
+        self.timesteps = self._grid[i0:]
+        self._write_start()
+        self._rewind()
 
     def _layout_for(self, cams):
         """The condition image rolled by the rotation these cameras carry (PanoGenerator.py:264-269)."""
@@ -378,7 +536,7 @@ class DenoiseLoop:
 
     def _dpmpp_update(self, eps, pano_eps, last, t_next):
         """The same two launches with the 2M correction; each writes its latent's x0 history (the panorama's rolled like the state)."""
-        coef, k, order = self.solver.step_coefficients(self.i)
+        coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
         second = order == 2
         ops.cfg_dpmpp_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
                                 x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat)
@@ -390,13 +548,14 @@ class DenoiseLoop:
         """The same two launches with the known-region blend after the DDIM or 2M update: x <- m x + (1 - m) r,
         r = add_noise(known, noise, t_next) = ka known + kb noise, known itself at the last step.  On this grid t_next is the DDIM
         target of the step, so (ka, kb) are the step's own (sqrt_a_prev, sqrt_1m_a_prev).  The panorama's operands are read at
-        the offset its state has been rolled by before this update: (i + 1) shifts (not total_rot, see result())."""
+        the offset its state has been rolled by before this update: (i + 1) shifts, i counting EXECUTED steps (not total_rot, see
+        result())."""
         ka, kb = (1.0, 0.0) if last else coef[2:]
         o = (self.i + 1) * self.shift % self.W
         blend = lambda z, n, m, roll: dict(known=z, noise=n, mask=m, ka=ka, kb=kb, known_roll=roll)
         x0 = dict(lat={}, pano={})
         if self.solver is not None:
-            coef, k, order = self.solver.step_coefficients(self.i)
+            coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
             second = order == 2
             x0 = dict(lat=dict(x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat),
                       pano=dict(x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano))

@@ -4,6 +4,8 @@ SD-2-base shapes, hipGraphs, bench.py's model and inputs).
     python tools/sampler_bench.py [--steps 20] [--repeats 2] [--out result.json]
     python tools/sampler_bench.py --profile          # short runs of both samplers, for rocprofv3 --kernel-trace --stats
     python tools/sampler_bench.py --known [--profile]  # DDIM without / with known content (inpainting)
+    python tools/sampler_bench.py --strength 0.5       # DDIM at strength 1 / at strength S from a source
+    python tools/sampler_bench.py --restart [--profile]  # set-up of another run: new loop + prepare() against restart()
 
 Prints one JSON line:
   * ms_per_step -- the loop step (denoiser graph replay + the two update launches) of each sampler, timed after warm-up
@@ -14,6 +16,16 @@ Fewer steps is what 2M is for; whether 2M-20/25 images match DDIM-50 in quality 
 
 With --known: ms_per_step of DDIM without and with a known region (a seeded panorama latent kept on half of the columns, its
 nearest e2p in the views), alternated the same way; --profile then runs 6 steps of each.
+
+With --strength S: ms_per_step of DDIM at strength 1 and at strength S (a seeded source panorama latent and its nearest e2p in
+the views; the grid is sized so that both run --warmup + --steps steps), alternated the same way, and time_to_latents_s of the
+50-step grid at strength 1 and at strength S (int(50 S) steps).
+
+With --restart: setup_ms -- wall time, to a synchronised device, of the two ways to set up another strength-S run (default 0.5)
+on the 50-step grid: ``new_loop_prepare`` = DenoiseLoop(...) + prepare() (tables cached by the first loop, one graph capture
+per rotation offset) and ``restart`` = DenoiseLoop.restart(new noise, new source) on a prepared loop; ``--repeats`` samples of
+each, alternated.  pf_noised_start_pair is a latency-bound launch over 1.4 MB here, not tuned for bandwidth: its time is the
+launch, see the kernel trace of --restart --profile (20 restarts, nothing else after the first prepare()).
 """
 import argparse
 import json
@@ -33,6 +45,8 @@ def main():
     ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"])
     ap.add_argument("--profile", action="store_true", help="6 steps of each sampler, no timing (run under rocprofv3)")
     ap.add_argument("--known", action="store_true", help="DDIM without / with known content instead of DDIM / 2M")
+    ap.add_argument("--strength", type=float, default=None, help="DDIM at strength 1 / at this strength instead of DDIM / 2M")
+    ap.add_argument("--restart", action="store_true", help="time DenoiseLoop + prepare() against restart() (set-up of another run)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -40,7 +54,7 @@ def main():
     import torch
     import bench
     from panfusion_amd.models.sd2_unet_params import SD2_BASE
-    from panfusion_amd.pipeline import DenoiseLoop, KnownRegion, init_noise
+    from panfusion_amd.pipeline import DenoiseLoop, KnownRegion, SourceLatents, init_noise
     from panfusion_amd.utils.pano import icosahedron_sample_camera
 
     dev = torch.device("cuda", 0)
@@ -59,15 +73,28 @@ def main():
         cams, (h, w) = inputs[-1], inputs[0].shape[-2:]
         known = KnownRegion(init_noise(pano_z, cams, h, w)[1], init_noise(pano_m, cams, h, w)[1], pano_z, pano_m)
 
+    def source(seed):
+        pano_z = torch.randn(inputs[1].shape, generator=torch.Generator().manual_seed(seed)).to(dev)
+        return SourceLatents(init_noise(pano_z, inputs[-1], *inputs[0].shape[-2:])[1], pano_z)
+
     def make(sampler, steps):
-        kn = None
+        kn, kw = None, {}
         if sampler == "ddim_known":
             sampler, kn = "ddim", known
-        loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler, known=kn)
+        if sampler == "ddim_strength":
+            # a grid on which strength S leaves exactly `steps` executed steps
+            n = next(n for n in range(steps, 1001) if min(int(n * args.strength), n) == steps)
+            sampler, steps, kw = "ddim", n, dict(strength=args.strength, init=source(5))
+        loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler, known=kn, **kw)
         loop.prepare()
         return loop
 
+    if args.restart:
+        return restart_bench(args, torch, DenoiseLoop, model, inputs, source)
+
     samplers = ("ddim", "ddim_known") if args.known else ("ddim", "dpmpp_2m")
+    if args.strength is not None:
+        samplers = ("ddim", "ddim_strength")
     if args.profile:
         for sampler in samplers:
             loop = make(sampler, 6)
@@ -94,8 +121,14 @@ def main():
 
     to_latents = {}
     runs = (("ddim_50", "ddim", 50), ("dpmpp_2m_25", "dpmpp_2m", 25), ("dpmpp_2m_20", "dpmpp_2m", 20))
+    if args.strength is not None:
+        runs = (("ddim_50", "ddim", 50), ("ddim_50_strength_%g" % args.strength, "ddim_strength", 50))
     for name, sampler, steps in (() if args.known else runs):
-        loop = make(sampler, steps)
+        if sampler == "ddim_strength":
+            loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, strength=args.strength, init=source(5))
+            loop.prepare()
+        else:
+            loop = make(sampler, steps)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         lat, pano = loop.run()
@@ -109,6 +142,61 @@ def main():
            "ms_per_step": {k: [round(v, 3) for v in vs] for k, vs in per_step.items()},
            "time_to_latents_s": {k: round(v, 4) for k, v in to_latents.items()},
            "note": "image quality at 20 / 25 steps of 2M vs 50 of DDIM: not measured"}
+    if args.strength is not None:
+        res["note"] = "image quality at strength %g: not measured" % args.strength
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def restart_bench(args, torch, DenoiseLoop, model, inputs, source):
+    import json
+    strength = 0.5 if args.strength is None else args.strength
+    noise = lambda seed: torch.randn(inputs[1].shape, generator=torch.Generator().manual_seed(seed)).to(inputs[1].device)
+
+    def fresh(seed):
+        from panfusion_amd.pipeline import init_noise
+        pano_n = noise(seed)
+        lat_n = init_noise(pano_n, inputs[-1], *inputs[0].shape[-2:])[1]
+        return lat_n, pano_n, source(seed + 100)
+
+    loop = DenoiseLoop(model, *inputs, steps=50, use_graphs=True, strength=strength, init=source(5))
+    loop.prepare()                                         # the first loop also builds the geometry tables: not a sample
+    loop.run()
+    torch.cuda.synchronize()
+    if args.profile:
+        for i in range(20):
+            lat_n, pano_n, src = fresh(i)
+            loop.restart(lat_n, pano_n, init=src)
+        torch.cuda.synchronize()
+        print(json.dumps({"profile": "20 restart() calls on a prepared cfg 2 loop"}))
+        return
+    setup = {"new_loop_prepare": [], "restart": []}
+    for i in range(args.repeats):
+        lat_n, pano_n, src = fresh(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        other = DenoiseLoop(model, lat_n, pano_n, *inputs[2:], steps=50, use_graphs=True, strength=strength, init=src)
+        other.prepare()
+        torch.cuda.synchronize()
+        setup["new_loop_prepare"].append((time.perf_counter() - t0) * 1e3)
+        want = other.run()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loop.restart(lat_n, pano_n, init=src)
+        torch.cuda.synchronize()
+        setup["restart"].append((time.perf_counter() - t0) * 1e3)
+        got = loop.run()
+        assert all(bool(torch.equal(a, b)) for a, b in zip(got, want)), "restart() and a fresh loop disagree"
+        del other, want, got
+        torch.cuda.empty_cache()
+    res = {"workload": "cfg2: 512x1024 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes, hipGraphs, %s; 50-step grid at "
+                       "strength %g" % (args.dtype, strength),
+           "setup_ms": {k: [round(v, 3) for v in vs] for k, vs in setup.items()},
+           "note": "restart() result checked bit for bit against the fresh loop of the same sample"}
     line = json.dumps(res)
     print(line)
     if args.out:
