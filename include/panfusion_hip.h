@@ -287,6 +287,25 @@ pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eps_uncond, cons
 pf_status pf_noised_start_pair(const float* z, const float* noise, float ka, float kb, long rows, int W, int roll,
                                float* out, float* out2, int64_t* tstep, int n_tstep, int64_t t0, void* stream);
 
+/* pf_noised_start_pair with z read from a SMALLER source: the start state of the second pass of two-pass high-resolution
+ * sampling ("hires fix": compose at the native size, up-sample the latents, re-noise, run the tail of the schedule).
+ * z: planes images (n * C) of h_src x w_src, fp32; the output is planes x H x W with H = fh h_src, W = fw w_src, fh and fw
+ * integers >= 1 (anything else is an error):
+ *   out[p][y][(w + roll) mod W] = fmaf(ka, r, kb * noise[p][y][w]),   r = resize(z[p])[y][w]
+ * and the same value to out2 (or NULL); noise == NULL: out = r itself, a pure resize (ka, kb unused).  tstep as above.
+ * resize is torch.nn.functional.interpolate(mode = nearest (0) / bilinear (1) / bicubic (2), align_corners=False, no
+ * antialiasing, cubic A = -0.75).  Rows clamp at the top and bottom.  wrap = 1: columns are periodic (a panorama latent: the
+ * taps of the output columns near 0 and W - 1 come from the other side of the source); wrap = 0: columns clamp (a view).
+ * The weights of an output index dst = q f + p depend on its phase p alone -- t = (2p + 1 - f) / (2f), its floor and its
+ * fraction, from integers -- so with wrap = 1 a source rolled by k columns gives the output rolled by k fw, bit for bit.  r is a
+ * complete fp32 value before the fmaf, the expression pf_noised_start_pair and the inpaint blend use: the result equals
+ * pf_noised_start_pair on the resized z bit for bit.
+ * One block per output row; the output row and the row-resampled source row are staged in LDS: W <= 2048 (16 KB at the limit).
+ * out / out2 must not alias z, noise or each other. */
+pf_status pf_upsampled_start_pair(const float* z, const float* noise, float ka, float kb, long planes, int h_src, int w_src,
+                                  int H, int W, int mode, int wrap, int roll, float* out, float* out2, int64_t* tstep,
+                                  int n_tstep, int64_t t0, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MFMA GEMM / implicit-GEMM convolution (replaces cuDNN/cuBLAS behind diffusers Conv2d/Linear:
  * MVGenModel.py:86-144,174-198,224-294 and transformer.py:57-74,8-38).

@@ -136,6 +136,8 @@ SIGNATURES = {
                                          c_int, c_void_p]),
     "pf_noised_start_pair": (c_int, [c_void_p, c_void_p, c_float, c_float, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_int, C.c_int64, c_void_p]),
+    "pf_upsampled_start_pair": (c_int, [c_void_p, c_void_p, c_float, c_float, c_long, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_void_p, c_void_p, c_int, C.c_int64, c_void_p]),
     "pf_conv_gemm":(c_int, [C.POINTER(ConvDesc), c_void_p]),
     "pf_conv_gemm_workspace_size": (c_size_t, [C.POINTER(ConvDesc)]),
     "pf_conv_gemm_gn_rows": (c_int, [C.POINTER(ConvDesc)]),

@@ -715,6 +715,100 @@ __global__ __launch_bounds__(256) void k_noised_start_rows(const float* __restri
         for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t0;
 }
 
+// ---- start state from a SMALLER source (two-pass high-resolution sampling) ----------------------
+// k_noised_start_rows with z read through a resize by integer factors (fh, fw): torch.nn.functional.interpolate's nearest /
+// bilinear / bicubic (align_corners=False, no antialiasing, cubic A = -0.75), rows clamped, columns clamped or periodic.
+// An output index dst = q f + p (phase p = dst mod f) has the source coordinate q + t, t = (2p + 1 - f) / (2f) in (-1/2, 1/2):
+// the tap offset floor(t) and the fraction t - floor(t) come from the INTEGERS p and f, one correctly rounded division, so the
+// weights of a phase are the same in every period and a periodic source rolled by k gives the output rolled by k f bit for bit
+// (a running scale * (dst + 0.5) - 0.5 in fp32 loses that: its error grows with dst).
+enum { PF_RESIZE_NEAREST = 0, PF_RESIZE_BILINEAR = 1, PF_RESIZE_BICUBIC = 2 };
+
+struct ResizeTap {         // taps i0 - 1 .. i0 + 2 around the source coordinate i0 + lam (nearest: i0 alone)
+    int i0;
+    float lam;
+};
+
+__device__ __forceinline__ ResizeTap resize_tap(int dst, int f, int mode) {
+    const int q = dst / f, num = 2 * (dst - q * f) + 1 - f;                   // t = num / (2f)
+    if (mode == PF_RESIZE_NEAREST) return {q, 0.f};
+    const int below = num < 0 ? 1 : 0;
+    return {q - below, static_cast<float>(num + below * 2 * f) / static_cast<float>(2 * f)};
+}
+
+__device__ __forceinline__ int resize_index(int i, int n, bool wrap) {
+    if (wrap) {
+        i %= n;
+        return i < 0 ? i + n : i;
+    }
+    return i < 0 ? 0 : (i >= n ? n - 1 : i);
+}
+
+// torch's cubic convolution coefficients (UpSample.h get_cubic_upsample_coefficients), A = -0.75
+__device__ __forceinline__ void cubic_weights(float t, float c[4]) {
+    const float A = -0.75f;
+    auto inner = [A](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };           // |x| <= 1
+    auto outer = [A](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };     // 1 < |x| < 2
+    c[0] = outer(t + 1.f);
+    c[1] = inner(t);
+    c[2] = inner(1.f - t);
+    c[3] = outer(2.f - t);
+}
+
+// One resampled value along one axis: sum_j c_j at(resize_index(i0 - 1 + j)).  Bilinear at a clamped low edge follows torch (a
+// negative source coordinate is 0: the first sample itself).  Both passes of the kernel -- and so the pure-resize and the noised
+// form -- go through this one function.
+template <typename At>
+__device__ __forceinline__ float resize_1d(ResizeTap tap, int n, bool wrap, int mode, At at) {
+    if (mode == PF_RESIZE_NEAREST) return at(resize_index(tap.i0, n, wrap));
+    if (mode == PF_RESIZE_BILINEAR) {
+        if (!wrap && tap.i0 < 0) tap = {0, 0.f};
+        const float a = at(resize_index(tap.i0, n, wrap)), b = at(resize_index(tap.i0 + 1, n, wrap));
+        return __builtin_fmaf(tap.lam, b, (1.f - tap.lam) * a);
+    }
+    float c[4];
+    cubic_weights(tap.lam, c);
+    float acc = c[0] * at(resize_index(tap.i0 - 1, n, wrap));
+    for (int j = 1; j < 4; ++j) acc = __builtin_fmaf(c[j], at(resize_index(tap.i0 - 1 + j, n, wrap)), acc);
+    return acc;
+}
+
+// One block per OUTPUT row (plane, y).  Pass 1: the source rows this output row needs, combined along y, one value per source
+// column, into LDS (coalesced reads of 1 / 2 / 4 source rows).  Pass 2: every output column resamples that row along x from LDS,
+// r is complete there; out[(w + roll) mod W] = noise ? fmaf(ka, r, kb * n) : r goes through the staged output row as in
+// k_noised_start_rows.  LDS: (w_src + W) floats.
+__global__ __launch_bounds__(256) void k_upsampled_start_rows(const float* __restrict__ z, const float* __restrict__ noise,
+                                                              float ka, float kb, int h_src, int w_src, int H, int W, int fh,
+                                                              int fw, int mode, int wrap, int roll, float* __restrict__ out,
+                                                              float* __restrict__ out2, long long* tstep, int n_tstep,
+                                                              long long t0) {
+    extern __shared__ float stage[];
+    float* src_row = stage;                  // w_src
+    float* row = stage + w_src;              // W
+    const long plane = blockIdx.x / H;
+    const int y = static_cast<int>(blockIdx.x - plane * H);
+    const float* zp = z + plane * h_src * w_src;
+    const ResizeTap ty = resize_tap(y, fh, mode);
+    for (int x = threadIdx.x; x < w_src; x += 256)
+        src_row[x] = resize_1d(ty, h_src, false, mode, [&](int yy) { return zp[static_cast<long>(yy) * w_src + x]; });
+    __syncthreads();
+    const long base = static_cast<long>(blockIdx.x) * W;
+    for (int w = threadIdx.x; w < W; w += 256) {
+        int wo = w + roll;
+        wo -= wo >= W ? W : 0;
+        const float r = resize_1d(resize_tap(w, fw, mode), w_src, wrap != 0, mode, [&](int xx) { return src_row[xx]; });
+        row[wo] = noise ? __builtin_fmaf(ka, r, kb * noise[base + w]) : r;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t0;
+}
+
 // ---- token + position embedding gather (CLIP text encoder, transformers CLIPTextEmbeddings) -------------
 // out[b][t][:] = tok[ids[b][t]][:] + pos[t][:] for t < L, zeros for the padding rows L <= t < Lp.
 template <typename SO>
@@ -1527,6 +1621,33 @@ extern "C" pf_status pf_noised_start_pair(const float* z, const float* noise, fl
                        as_stream(stream), z, noise, ka, kb, W, r, out, out2, reinterpret_cast<long long*>(tstep), n_tstep,
                        static_cast<long long>(t0));
     PF_CHECK_LAUNCH("pf_noised_start_pair");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_upsampled_start_pair(const float* z, const float* noise, float ka, float kb, long planes, int h_src,
+                                             int w_src, int H, int W, int mode, int wrap, int roll, float* out, float* out2,
+                                             int64_t* tstep, int n_tstep, int64_t t0, void* stream) {
+    PF_REQUIRE(z && out && planes > 0 && h_src > 0 && w_src > 0 && H > 0 && W > 0,
+               "pf_upsampled_start_pair: bad arguments (z and out are required)");
+    PF_REQUIRE(mode == PF_RESIZE_NEAREST || mode == PF_RESIZE_BILINEAR || mode == PF_RESIZE_BICUBIC,
+               "pf_upsampled_start_pair: mode %d is not 0 (nearest), 1 (bilinear) or 2 (bicubic)", mode);
+    PF_REQUIRE(H % h_src == 0 && W % w_src == 0,
+               "pf_upsampled_start_pair: %d x %d is not an integer multiple of the source's %d x %d (integer factors >= 1 only)",
+               H, W, h_src, w_src);
+    PF_REQUIRE(W <= 2048 && H <= 65536, "pf_upsampled_start_pair: W=%d must be <= 2048 (the output row and the resampled source row "
+               "of a block are staged in LDS) and H=%d <= 65536", W, H);
+    PF_REQUIRE(planes * H < (1L << 31), "pf_upsampled_start_pair: planes=%ld x H=%d must be < 2^31 (one block per output row)", planes, H);
+    PF_REQUIRE(out2 != out, "pf_upsampled_start_pair: out2 must be a buffer of its own");
+    PF_REQUIRE(out != z && out2 != z && (!noise || (out != noise && out2 != noise)),
+               "pf_upsampled_start_pair: out / out2 must not alias z or noise (__restrict__ operands)");
+    PF_REQUIRE(!tstep || n_tstep > 0, "pf_upsampled_start_pair: n_tstep must be positive with tstep");
+    int r = roll % W;
+    if (r < 0) r += W;
+    hipLaunchKernelGGL(k_upsampled_start_rows, dim3(static_cast<unsigned>(planes * H)), dim3(256),
+                       static_cast<size_t>(w_src + W) * sizeof(float), as_stream(stream), z, noise, ka, kb, h_src, w_src, H, W,
+                       H / h_src, W / w_src, mode, wrap, r, out, out2, reinterpret_cast<long long*>(tstep), n_tstep,
+                       static_cast<long long>(t0));
+    PF_CHECK_LAUNCH("pf_upsampled_start_pair");
     return PF_OK;
 }
 

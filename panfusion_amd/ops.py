@@ -512,6 +512,40 @@ def noised_start_pair(z, noise, ka, kb, roll=0, *, out, out2=None, tstep=None, t
     return out
 
 
+RESIZE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+
+
+def upsampled_start_pair(z, noise, ka, kb, roll=0, *, mode, wrap, out, out2=None, tstep=None, t0=0):
+    """noised_start_pair with ``z`` (..., h, w) SMALLER than ``out`` (..., H, W) by integer factors: ``out`` <-
+    ka r + kb noise rolled by ``roll``, r = torch's interpolate(z, (H, W), mode, align_corners=False) with clamped rows and --
+    ``wrap=True`` -- periodic columns (a panorama latent; ``wrap=False`` clamps them: a view).  ``noise=None``: r itself, a pure
+    resize.  ``mode``: "nearest", "bilinear" or "bicubic".  The leading dimensions of z and out must be equal."""
+    if mode not in RESIZE_MODES:
+        raise ValueError("resample mode must be one of %s, got %r" % (sorted(RESIZE_MODES), mode))
+    (h, w), (H, W) = z.shape[-2:], out.shape[-2:]
+    planes = z.numel() // (h * w)
+    assert tuple(z.shape[:-2]) == tuple(out.shape[:-2]), (z.shape, out.shape)
+    for t in (z, noise, out, out2):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32)
+    for t in (noise, out2):
+        assert t is None or t.numel() == out.numel()
+    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    opt = lambda t: _p(t) if t is not None else None
+    check(_lib.lib().pf_upsampled_start_pair(_p(z), opt(noise), float(ka), float(kb), planes, h, w, H, W, RESIZE_MODES[mode],
+                                             int(bool(wrap)), int(roll), _p(out), opt(out2), opt(tstep),
+                                             tstep.numel() if tstep is not None else 0, int(t0), _stream()),
+          "pf_upsampled_start_pair")
+    return out
+
+
+def resize_latent(x, size, mode="bicubic", wrap=False, out=None):
+    """x fp32 (..., h, w) -> (..., *size), integer factors: upsampled_start_pair's resize alone (``noise=None``)."""
+    if out is None:
+        out = torch.empty(tuple(x.shape[:-2]) + tuple(size), device=x.device, dtype=torch.float32)
+    assert tuple(out.shape[-2:]) == tuple(size)
+    return upsampled_start_pair(x, None, 0.0, 0.0, 0, mode=mode, wrap=wrap, out=out)
+
+
 # ---------------------------------------------------------------------------- GEMM / conv
 def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, stride=1, pad=0, upsample=0,
               bias=None, rowvec=None, residual=None, out=None, out_dtype=None, batch=1,

@@ -14,6 +14,9 @@ known content into the state inside the same two update launches
 starts from a noised source and runs the last ``int(steps * s)`` steps of the grid
 (image-to-panorama, partial-strength inpainting), and ``restart()`` re-arms a loop
 in place -- same buffers, same captured graphs -- for the next run.
+``SourceLatents(..., resample="bicubic")`` admits a source smaller than the loop by integer factors, up-sampled inside the
+start launch (periodic in longitude for the panorama), and ``HiResLoop`` chains a base pass and a refine pass at a larger
+size on one model: two-pass high-resolution sampling.
 """
 import copy
 import math
@@ -163,13 +166,21 @@ def _check_shapes(what, named, batch):
             raise ValueError("%s: %s must be %s, got %s" % (what, name, shape, getattr(t, "shape", type(t))))
 
 
+RESAMPLE_MODES = ("nearest", "bilinear", "bicubic")
+
+
 class SourceLatents:
     """The clean source latents z of a strength < 1 run: latents (1, m, 4, h, w) for the views and pano_latent
     (1, 1, 4, H, W) for the panorama, in the caller's (un-rotated) frame.  ``DenoiseLoop(..., strength=s, init=...)`` starts
-    from add_noise(z, noise, t_s) and checks the shapes against its latents."""
+    from add_noise(z, noise, t_s) and checks the shapes against its latents.
+    ``resample`` ("nearest", "bilinear" or "bicubic"): the source may be SMALLER than the loop's latents by integer
+    factors, views and panorama independently; the start launch up-samples it with torch's interpolate semantics
+    (align_corners=False), the panorama periodic in longitude, the views clamped.  None: the shapes must be equal."""
 
-    def __init__(self, latents, pano_latent):
-        self.latents, self.pano_latent = latents, pano_latent
+    def __init__(self, latents, pano_latent, resample=None):
+        if resample is not None and resample not in RESAMPLE_MODES:
+            raise ValueError("SourceLatents: resample must be None or one of %s, got %r" % (RESAMPLE_MODES, resample))
+        self.latents, self.pano_latent, self.resample = latents, pano_latent, resample
 
     @classmethod
     def from_panorama(cls, vae_encoder, pano, cameras, view_hw, latent_pad=8):
@@ -180,9 +191,19 @@ class SourceLatents:
         return cls(*_encode_panorama(vae_encoder, pano, cameras, view_hw, latent_pad))
 
     def check(self, latents, pano_latent):
-        """ValueError unless the source fits the loop's latents (batch 1)."""
+        """ValueError unless the source fits the loop's latents (batch 1): equal shapes, or -- with ``resample`` -- equal
+        leading dimensions and a height and width that divide the loop's."""
         lat, pano = tuple(latents.shape), tuple(pano_latent.shape)
-        _check_shapes("source latents", (("latents", self.latents, lat), ("pano_latent", self.pano_latent, pano)), (lat, pano))
+        if self.resample is None:
+            _check_shapes("source latents", (("latents", self.latents, lat), ("pano_latent", self.pano_latent, pano)), (lat, pano))
+            return
+        _check_shapes("source latents", (), (lat, pano))
+        for name, t, shape in (("latents", self.latents, lat), ("pano_latent", self.pano_latent, pano)):
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else None
+            if got is None or len(got) != len(shape) or got[:-2] != shape[:-2] or min(got[-2:]) < 1 \
+                    or shape[-2] % got[-2] or shape[-1] % got[-1]:
+                raise ValueError("source latents: %s must be %s or smaller by integer factors in height and width (resample=%r), "
+                                 "got %s" % (name, shape, self.resample, getattr(t, "shape", type(t))))
 
 
 def executed_steps(steps, strength):
@@ -318,9 +339,10 @@ class DenoiseLoop:
         self._owns_noise = known is not None or k < steps
         self.noise_lat, self.noise_pano = (own(latents), own(pano_latent)) if self._owns_noise else (latents, pano_latent)
         # the source z of a strength < 1 start: the loop's own copy of init, else the known latents themselves
-        self.src_lat = self.src_pano = None
+        # (its own size with init.resample: the start kernel up-samples it)
+        self.src_lat = self.src_pano = self.resample = None
         if init is not None:
-            self.src_lat, self.src_pano = own(init.latents), own(init.pano_latent)
+            self.src_lat, self.src_pano, self.resample = own(init.latents), own(init.pano_latent), init.resample
         self.tstep = torch.empty(2, self.m, dtype=torch.long, device=dev)
         self.use_graphs = use_graphs
         self.graphs = {}
@@ -364,15 +386,25 @@ class DenoiseLoop:
             ka, kb = self.sched.coefficients(t0)[:2]
             z_lat, z_pano = (self.known_lat, self.known_pano) if self.src_lat is None else (self.src_lat, self.src_pano)
         roll = self.shift if self.rot_diff % 360 else 0
-        ops.noised_start_pair(z_lat, self.noise_lat, ka, kb, 0, out=self.lat, out2=self.lat2[1:])
-        ops.noised_start_pair(z_pano, self.noise_pano, ka, kb, roll, out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t0=t0)
+        self._start_launch(z_lat, self.noise_lat, ka, kb, 0, False, out=self.lat, out2=self.lat2[1:])
+        self._start_launch(z_pano, self.noise_pano, ka, kb, roll, True, out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t0=t0)
         self._tstep_value = t0
+
+    def _start_launch(self, z, noise, ka, kb, roll, wrap, **out):
+        """One start launch: noised_start_pair, or -- for a source smaller than the latent -- the launch that
+        up-samples it on the way, periodic in longitude (``wrap``) for the panorama."""
+        if z is None or z.shape[-2:] == noise.shape[-2:]:
+            ops.noised_start_pair(z, noise, ka, kb, roll, **out)
+        else:
+            ops.upsampled_start_pair(z, noise, ka, kb, roll, mode=self.resample, wrap=wrap, **out)
 
     def restart(self, latents=None, pano_latent=None, *, strength=None, init=None, known=None):
         """Back to "constructed, before the first step" IN PLACE: state pair, timestep words, step counters, cameras, total_rot,
         the 2M order; and -- where given -- new noise, a new source, new known contents (same shapes, copied into the loop's own
         operand buffers) and a new strength.  None keeps the current value.  Captured graphs, EPA tables and pinned text K/V stay
-        valid: no buffer a graph reads is allocated and no address changes.  Not re-armable: steps, sampler, rot_diff, guidance,
+        valid: no buffer a graph reads is allocated and no address changes.  A new source may have another admissible size
+        (``SourceLatents(..., resample=)``): the source buffers are operands of the start launch only, so they
+        are re-allocated then.  Not re-armable: steps, sampler, rot_diff, guidance,
         prompts, cameras, and whether the loop has known content at all."""
         shape_lat, shape_pano = (1,) + tuple(self.lat.shape[1:]), (1,) + tuple(self.pano.shape[1:])
         like_lat, like_pano = torch.empty(shape_lat, device="meta"), torch.empty(shape_pano, device="meta")
@@ -409,10 +441,11 @@ class DenoiseLoop:
             put(self.mask_lat, known.mask.expand_as(self.mask_lat))
             put(self.mask_pano, known.pano_mask.expand_as(self.mask_pano))
         if init is not None:
-            if self.src_lat is None:
-                self.src_lat, self.src_pano = torch.empty_like(self.noise_lat), torch.empty_like(self.noise_pano)
-            put(self.src_lat, init.latents)
-            put(self.src_pano, init.pano_latent)
+            own = lambda t: t.detach().to(dev, torch.float32).clone(memory_format=torch.contiguous_format)
+            fits = lambda buf, t: buf is not None and buf.shape == t.shape
+            self.src_lat = put(self.src_lat, init.latents) if fits(self.src_lat, init.latents) else own(init.latents)
+            self.src_pano = put(self.src_pano, init.pano_latent) if fits(self.src_pano, init.pano_latent) else own(init.pano_latent)
+            self.resample = init.resample
         self.strength, self.i0 = new_strength, i0
         self.timesteps = self._grid[i0:]
         self._write_start()
@@ -574,6 +607,67 @@ class DenoiseLoop:
         """Latents with the accumulated rotation undone (PanFusion.py:164)."""
         back = int(-self.total_rot / 360 * self.W)
         return self.lat, ops.roll_width(self.pano, back)
+
+
+class HiResLoop:
+    """Two-pass high-resolution sampling: a BASE pass from noise at the size the UNets were trained for, then a
+    REFINE pass at a larger size that starts from the base result up-sampled (the panorama periodic in longitude), re-noised to
+    the timestep ``strength`` selects, and runs only the tail of its schedule.  It owns two DenoiseLoops on the one model;
+    ``run()`` is base.run(), refine.restart(init=SourceLatents(*base.result(), resample=...)), refine.run().  base.result() is in
+    the caller's un-rotated frame, which is the frame SourceLatents is defined in: the rotation the base pass accumulated never
+    reaches the refine pass.
+
+    base_noise / noise: (latents, pano_latent) NOISE pairs at the base and at the final size (DenoiseLoop's first two
+    arguments); every final dimension is an integer multiple of the base one, views and panorama independently.  Views of the
+    same size in both passes (20 x 64 x 64 at 512x1024 -> 1024x2048) are passed through without resampling.
+    steps: the base grid; refine_steps: the refine grid (default: steps), of which int(refine_steps * strength) run;
+    resample: "nearest", "bilinear" or "bicubic"; the other arguments as DenoiseLoop takes them, for both passes.
+    Known regions and layout conditioning are NOT taken here: compose two DenoiseLoops by hand for them, the second with
+    init=SourceLatents(..., resample=)."""
+
+    def __init__(self, model, base_noise, noise, prompt_embd, pano_prompt_embd, cameras, *, steps=50, refine_steps=None,
+                 strength=0.5, resample="bicubic", sampler="ddim", guidance_scale=9.0, rot_diff=90.0, use_graphs=False):
+        refine_steps = steps if refine_steps is None else refine_steps
+        self._check_strength(refine_steps, strength)
+        self.resample = resample
+        # the refine loop's source buffers, at the size base.result() will have: checks the sizes against each other too
+        placeholder = SourceLatents(torch.zeros_like(base_noise[0]), torch.zeros_like(base_noise[1]), resample=resample)
+        placeholder.check(*noise)
+        common = dict(rot_diff=rot_diff, guidance_scale=guidance_scale, use_graphs=use_graphs, sampler=sampler)
+        self.base = DenoiseLoop(model, base_noise[0], base_noise[1], prompt_embd, pano_prompt_embd, cameras, steps=steps, **common)
+        self.refine = DenoiseLoop(model, noise[0], noise[1], prompt_embd, pano_prompt_embd, cameras, steps=refine_steps,
+                                  strength=strength, init=placeholder, **common)
+
+    @staticmethod
+    def _check_strength(refine_steps, strength):
+        if executed_steps(refine_steps, strength)[0] == refine_steps:
+            raise ValueError("HiResLoop: strength %r runs the whole refine grid of %d from noise and ignores the base pass; "
+                             "it must be < 1" % (strength, refine_steps))
+
+    def prepare(self):
+        """Untimed set-up of both passes: geometry tables and (use_graphs) one captured graph per rotation offset and size."""
+        self.base.prepare()
+        self.refine.prepare()
+
+    def run(self):
+        z = self.base.run()
+        self.refine.restart(init=SourceLatents(*z, resample=self.resample))
+        return self.refine.run()
+
+    def restart(self, base_noise=None, noise=None, strength=None):
+        """Re-arm both loops in place for the next seed (DenoiseLoop.restart: same buffers, same graphs); None keeps the value."""
+        base_noise, noise = base_noise or (None, None), noise or (None, None)
+        if strength is not None:
+            self._check_strength(self.refine.steps, strength)
+        for loop, pair in ((self.base, base_noise), (self.refine, noise)):           # all checks before anything changes
+            shapes = tuple((1,) + tuple(t.shape[1:]) for t in (loop.lat, loop.pano))
+            _check_shapes("restart", [(n, t, s) for n, t, s in zip(("latents", "pano_latent"), pair, shapes) if t is not None],
+                          shapes)
+        self.base.restart(*base_noise)
+        self.refine.restart(*noise, strength=strength)
+
+    def result(self):
+        return self.refine.result()
 
 
 def add_noise(sched, x, noise, t):

@@ -6,6 +6,7 @@ SD-2-base shapes, hipGraphs, bench.py's model and inputs).
     python tools/sampler_bench.py --known [--profile]  # DDIM without / with known content (inpainting)
     python tools/sampler_bench.py --strength 0.5       # DDIM at strength 1 / at strength S from a source
     python tools/sampler_bench.py --restart [--profile]  # set-up of another run: new loop + prepare() against restart()
+    python tools/sampler_bench.py --hires [--profile]    # two-pass 512x1024 -> 1024x2048 (HiResLoop)
 
 Prints one JSON line:
   * ms_per_step -- the loop step (denoiser graph replay + the two update launches) of each sampler, timed after warm-up
@@ -26,6 +27,14 @@ on the 50-step grid: ``new_loop_prepare`` = DenoiseLoop(...) + prepare() (tables
 per rotation offset) and ``restart`` = DenoiseLoop.restart(new noise, new source) on a prepared loop; ``--repeats`` samples of
 each, alternated.  pf_noised_start_pair is a latency-bound launch over 1.4 MB here, not tuned for bandwidth: its time is the
 launch, see the kernel trace of --restart --profile (20 restarts, nothing else after the first prepare()).
+
+With --hires: cfg 2 -> cfg 4 (the 64x128 panorama latent up-sampled to 128x256 under the same 20 views of 64x64 latents), graphs.
+time_to_latents_s of HiResLoop.run() -- base pass, re-arming the refine loop from its result, refine pass -- with DDIM at
+--base-steps 50 and with 2M at 20, strength --strength (default 0.5), and of a direct 50-step cfg 4 run from noise for
+orientation; restart_ms -- wall time of HiResLoop.restart(new noise for both passes) to a synchronised device, ``--repeats``
+samples.  --profile instead makes 20 launches each of upsampled_start_pair (bicubic, wrapped, the cfg 4 panorama latent) and of
+the unfused pair it replaces, resize_latent + noised_start_pair, for rocprofv3 --kernel-trace --stats.  Image quality of the
+two-pass result against the direct run is NOT measured (no trained weights).
 """
 import argparse
 import json
@@ -47,6 +56,8 @@ def main():
     ap.add_argument("--known", action="store_true", help="DDIM without / with known content instead of DDIM / 2M")
     ap.add_argument("--strength", type=float, default=None, help="DDIM at strength 1 / at this strength instead of DDIM / 2M")
     ap.add_argument("--restart", action="store_true", help="time DenoiseLoop + prepare() against restart() (set-up of another run)")
+    ap.add_argument("--hires", action="store_true", help="two-pass cfg 2 -> cfg 4 through HiResLoop (DESIGN.md §4.8)")
+    ap.add_argument("--base-steps", type=int, default=50, help="--hires: the DDIM grid of both passes (2M runs 20)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -89,6 +100,9 @@ def main():
         loop.prepare()
         return loop
 
+    if args.hires:
+        big = bench.build_inputs(dev, 20, (64, 64), (128, 256), cfg["cross_attention_dim"], (np.degrees(th), np.degrees(ph)))
+        return hires_bench(args, torch, model, inputs, big)
     if args.restart:
         return restart_bench(args, torch, DenoiseLoop, model, inputs, source)
 
@@ -197,6 +211,68 @@ def restart_bench(args, torch, DenoiseLoop, model, inputs, source):
                        "strength %g" % (args.dtype, strength),
            "setup_ms": {k: [round(v, 3) for v in vs] for k, vs in setup.items()},
            "note": "restart() result checked bit for bit against the fresh loop of the same sample"}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def hires_bench(args, torch, model, inputs, big):
+    import json
+    from panfusion_amd import ops
+    from panfusion_amd.pipeline import DenoiseLoop, HiResLoop, init_noise
+    strength = 0.5 if args.strength is None else args.strength
+    dev = inputs[1].device
+    if args.profile:
+        z = torch.randn(inputs[1].shape, generator=torch.Generator().manual_seed(5)).to(dev)
+        n, out, out2, tmp = big[1], torch.empty_like(big[1]), torch.empty_like(big[1]), torch.empty_like(big[1])
+        for _ in range(20):
+            ops.upsampled_start_pair(z, n, 0.6, 0.8, 64, mode="bicubic", wrap=True, out=out, out2=out2)
+        for _ in range(20):
+            ops.noised_start_pair(ops.resize_latent(z, n.shape[-2:], "bicubic", True, out=tmp), n, 0.6, 0.8, 64, out=out, out2=out2)
+        torch.cuda.synchronize()
+        print(json.dumps({"profile": "20 x pf_upsampled_start_pair and 20 x (resize_latent + pf_noised_start_pair), 64x128 -> 128x256"}))
+        return
+
+    def noise(seed, like):
+        pano_n = torch.randn(like[1].shape, generator=torch.Generator().manual_seed(seed)).to(dev)
+        return init_noise(pano_n, inputs[-1], *like[0].shape[-2:])[1], pano_n
+
+    to_latents, restart_ms = {}, []
+    for name, sampler, steps in (("hires_ddim_%d" % args.base_steps, "ddim", args.base_steps), ("hires_dpmpp_2m_20", "dpmpp_2m", 20)):
+        loop = HiResLoop(model, inputs[:2], big[:2], *inputs[2:], steps=steps, strength=strength, sampler=sampler, use_graphs=True)
+        loop.prepare()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lat, pano = loop.run()
+        torch.cuda.synchronize()
+        to_latents[name] = time.perf_counter() - t0
+        assert bool(torch.isfinite(lat).all()) and bool(torch.isfinite(pano).all()), name
+        graphs = [dict(loop.base.graphs), dict(loop.refine.graphs)]
+        for i in range(args.repeats if sampler == "ddim" else 0):
+            base_n, n = noise(10 + i, inputs), noise(20 + i, big)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loop.restart(base_n, n)
+            torch.cuda.synchronize()
+            restart_ms.append((time.perf_counter() - t0) * 1e3)
+        assert all(lp.graphs[k] is g[k] for lp, g in zip((loop.base, loop.refine), graphs) for k in g)
+        del loop, lat, pano
+        torch.cuda.empty_cache()
+    direct = DenoiseLoop(model, *big, steps=50, use_graphs=True)
+    direct.prepare()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    direct.run()
+    torch.cuda.synchronize()
+    to_latents["direct_cfg4_ddim_50"] = time.perf_counter() - t0
+    res = {"workload": "cfg2 -> cfg4: 512x1024 -> 1024x2048 pano + 20x512^2 views, CFG pair, SD-2-base UNet shapes, hipGraphs, %s; "
+                       "strength %g, bicubic" % (args.dtype, strength),
+           "time_to_latents_s": {k: round(v, 4) for k, v in to_latents.items()},
+           "restart_ms": [round(v, 3) for v in restart_ms],
+           "note": "image quality of the two-pass result against the direct run: not measured"}
     line = json.dumps(res)
     print(line)
     if args.out:
