@@ -102,10 +102,10 @@ def e2p_grid(eh, ew, fov, theta, phi, h, w):
 # ----------------------------------------------------------------------------
 # panorama pixel -> perspective image  (p2e.py:9-49)
 # ----------------------------------------------------------------------------
-def p2e_grid(ph, pw, wfov, theta, phi, h, w):
-    """For every pixel of an (h,w) panorama: sampling position in the (ph,pw)
-    view (0 where not visible) and the visibility mask.  Note u in [0,pw],
-    v in [0,ph] (NOT pw-1): p2e.py:41-44."""
+def p2e_view_rays(ph, pw, wfov, theta, phi, h, w):
+    """p2e.py:9-39: for every pixel of an (h,w) panorama its ray in the frame of
+    the (ph,pw) view, float64: (x, y / x, z / x, w_len, h_len).  The view shows
+    the pixel where x > 0, -w_len < y / x < w_len and -h_len < z / x < h_len."""
     hfov = float(ph) / pw * wfov
     w_len = np.tan(math.radians(wfov / 2.0))
     h_len = np.tan(math.radians(hfov / 2.0))
@@ -119,11 +119,20 @@ def p2e_grid(ph, pw, wfov, theta, phi, h, w):
     R2i = np.linalg.inv(R2)
     v = d.reshape(-1, 3).T
     v = np.dot(R1i, np.dot(R2i, v)).T.reshape(h, w, 3)
-    front = v[..., 0] > 0
+    x = v[..., 0].copy()
     v = v / v[..., 0:1]
-    inside = (-w_len < v[..., 1]) & (v[..., 1] < w_len) & (-h_len < v[..., 2]) & (v[..., 2] < h_len)
-    u = np.where(inside, (v[..., 1] + w_len) / 2 / w_len * pw, 0)
-    vv = np.where(inside, (-v[..., 2] + h_len) / 2 / h_len * ph, 0)
+    return x, v[..., 1], v[..., 2], w_len, h_len
+
+
+def p2e_grid(ph, pw, wfov, theta, phi, h, w):
+    """For every pixel of an (h,w) panorama: sampling position in the (ph,pw)
+    view (0 where not visible) and the visibility mask.  Note u in [0,pw],
+    v in [0,ph] (NOT pw-1): p2e.py:41-44."""
+    x, yy, zz, w_len, h_len = p2e_view_rays(ph, pw, wfov, theta, phi, h, w)
+    front = x > 0
+    inside = (-w_len < yy) & (yy < w_len) & (-h_len < zz) & (zz < h_len)
+    u = np.where(inside, (yy + w_len) / 2 / w_len * pw, 0)
+    vv = np.where(inside, (-zz + h_len) / 2 / h_len * ph, 0)
     return u, vv, inside & front
 
 

@@ -90,6 +90,81 @@ def test_masks_coords_pe(ref):
         assert_within_one_ulp(G.spherical_pe(b[0], fb).reshape(-1)[ref["pe%d_idx" % n]].numpy(), ref["pe%d_val" % n])
 
 
+# ---- the same operators off the benchmark grid: tests/golden/geometry_cameras.npz (tools/make_golden_geometry.py) holds the
+# reference's answers for 34 cameras of any field of view, yaw and pitch (poles, seam, yaw outside one turn), non-square views
+E2P_SIZES = ((16, 32, 16, 16), (32, 64, 12, 20), (17, 33, 9, 7), (64, 128, 32, 32))        # (eh, ew, h, w)
+P2E_SIZES = ((16, 16, 16, 32), (12, 20, 32, 64), (9, 7, 17, 33))                           # (ph, pw, H, W)
+MASK_SETS = (("cams5", (8, 8, 8, 16)), ("cams5", (6, 10, 8, 16)), ("cams5", (4, 4, 4, 8)), ("first13", (4, 4, 4, 8)))
+
+
+@pytest.fixture(scope="module")
+def geo():
+    return golden("geometry_cameras.npz")
+
+
+def _camera_dict(c):
+    return {"FoV": torch.tensor(c[:, 0]), "theta": torch.tensor(c[:, 1]), "phi": torch.tensor(c[:, 2])}
+
+
+def test_camera_list_of_the_geometry_fixture(geo):
+    c = geo["cams"]
+    assert c.shape == (34, 3) and c.dtype == np.float64
+    assert 35 <= c[:24, 0].min() and c[:24, 0].max() <= 130 and c[:24, 1].min() < 0 and c[:24, 1].max() > 360
+    assert [tuple(r) for r in c[24:29]] == [(90, 0, 0), (90, 0, 90), (90, 0, -90), (90, 180, 0), (90, 360, 0)]
+    assert [tuple(r) for r in c[29:]] == [(90, -180, 45), (120, 359.999, 89.9), (60, 360 / 7, 0), (150, 12.5, -30), (20, 270, 10)]
+    assert np.array_equal(geo["cams5"].T, [[90, 70, 110, 90, 60], [0, 33.3, 200, -45, 123.4], [0, 90, -60, 20, -89]])
+
+
+@pytest.mark.parametrize("size", E2P_SIZES)
+def test_e2p_grids_bit_exact_off_benchmark_cameras(geo, size):
+    eh, ew, h, w = size
+    maps = [G.e2p_grid(eh, ew, f, t, p, h, w) for f, t, p in geo["cams"]]
+    bad = [i for i, m in enumerate(maps) if not np.array_equal(digest(*m), geo["e2p_grid_%dx%d_%dx%d" % size][i])]
+    assert not bad, "cameras %s differ from the reference at %s" % (bad, size)
+    if size == (17, 33, 9, 7):
+        assert np.array_equal(np.stack([np.stack(m) for m in maps]), geo["e2p_maps_17x33_9x7"])
+
+
+@pytest.mark.parametrize("size", P2E_SIZES)
+def test_p2e_grids_and_masks_bit_exact_off_benchmark_cameras(geo, size):
+    ph, pw, H, W = size
+    key = "%dx%d_%dx%d" % size
+    maps = [G.p2e_grid(ph, pw, f, t, p, H, W) for f, t, p in geo["cams"]]
+    want_mask = np.unpackbits(geo["p2e_mask_" + key])[:34 * H * W].reshape(34, H, W).astype(bool)
+    assert np.array_equal(np.stack([m[2] for m in maps]), want_mask)
+    bad = [i for i, m in enumerate(maps) if not np.array_equal(digest(*m), geo["p2e_grid_" + key][i])]
+    assert not bad, "cameras %s differ from the reference at %s" % (bad, size)
+    if size == (9, 7, 17, 33):
+        assert np.array_equal(np.stack([np.stack(m[:2]) for m in maps]), geo["p2e_maps_9x7_17x33"])
+
+
+def test_remap_off_benchmark_cameras_non_square_view(geo):
+    """e2p.py:54-76 / p2e.py:52-71 with one camera per sample: a 32x64 panorama and 12x20 views (hfov = h / w * fov)."""
+    rng = np.random.default_rng(8)
+    pano = torch.from_numpy(rng.standard_normal((34, 3, 32, 64)).astype(np.float32))
+    views = torch.from_numpy(rng.standard_normal((34, 3, 12, 20)).astype(np.float32))
+    cams = [torch.tensor(geo["cams"][:, k]) for k in range(3)]
+    for mode in ("nearest", "bilinear"):
+        assert np.array_equal(digest(G.e2p(pano, *cams, (12, 20), mode=mode)), geo["remap_e2p_" + mode]), mode
+        assert np.array_equal(digest(*G.p2e(views, *cams, (32, 64), mode=mode)), geo["remap_p2e_" + mode]), mode
+
+
+@pytest.mark.parametrize("which,shape", MASK_SETS)
+def test_masks_off_benchmark_cameras(geo, which, shape):
+    """models/pano/utils.py:10-84 with P = 16 and P = 60 (m * P no multiple of 32), pole cameras, m = 13."""
+    c = geo["cams5"] if which == "cams5" else geo["cams"][:13]
+    name = "%s_%dx%d_%dx%d" % ((which,) + shape)
+    pers, equi = G.get_masks(*shape, _camera_dict(c))
+    assert np.array_equal(digest(pers, equi), geo["masks_%s_digest" % name])
+    assert np.array_equal(pers.numpy(), geo["masks_%s_pers" % name]) and np.array_equal(equi.numpy(), geo["masks_%s_equi" % name])
+
+
+def test_coords_off_benchmark_cameras(geo):
+    pers, equi = G.get_coords(12, 20, 16, 32, _camera_dict(geo["cams"]))
+    assert np.array_equal(digest(pers, equi), geo["coords_digest"])
+    assert np.array_equal(pers.numpy(), geo["coords_pers"]) and np.array_equal(equi.numpy(), geo["coords_equi"])
+
+
 def test_pad_unpad(ref):
     g = torch.Generator().manual_seed(32)
     xs = (torch.randn(2, 3, 5, 16, generator=g), torch.randn(2, 2, 3, 5, 16, generator=g))
