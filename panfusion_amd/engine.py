@@ -766,6 +766,23 @@ def _epa_tail(e, attn_out, x, Cc):
     return ops.linear(g, e.w_ff2, bias=e.b_ff2, residual=y, gn_stats=True)
 
 
+def band_flags_p(t, r0, r1):
+    """Tile-flag map of the view-query rows [r0, r1) of an EPATables entry `t` (bias_p [m*P, E], flags_p): the map the attention
+    kernel reads next to bias_p[r0:r1], whose flag row j covers the LOCAL rows [32 j, 32 j + 32)."""
+    if r0 % 32 == 0:
+        return t.flags_p[r0 // 32:(r1 + 31) // 32]
+    # view-group boundary inside a 32-row flag tile (only at toy sizes, P < 32): re-derive the tile
+    # map of the local rows from the table itself (one-off table preparation, not step arithmetic)
+    key = ("flags_p_loc", r0, r1)
+    if key not in t.__dict__:
+        rows = t.bias_p[r0:r1]
+        E = rows.shape[1]
+        pad = torch.nn.functional.pad(rows, (0, (-E) % 32, 0, (-(r1 - r0)) % 32))
+        t.__dict__[key] = (pad.reshape(pad.shape[0] // 32, 32, pad.shape[1] // 32, 32).abs().amax((1, 3)) > 0) \
+            .to(torch.uint8).contiguous()
+    return t.__dict__[key]
+
+
 def run_epa_sharded(e, t, xp, xe, m, shard, equi_hw=None, pers_hw=None, posted=None):
     """EPA when this rank holds views [v0, v1) of the m (one CFG sample per rank, b == 1).
     One all-gather of LN1(x_p + PE) inside the CFG half; K / V^T of all views are projected locally.
@@ -797,17 +814,7 @@ def run_epa_sharded(e, t, xp, xe, m, shard, equi_hw=None, pers_hw=None, posted=N
     mP = m * P
     v0, v1 = shard.views
     r0, r1 = v0 * P, v1 * P
-    flags_p_loc = t.flags_p[r0 // 32:(r1 + 31) // 32]
-    if r0 % 32:
-        # view-group boundary inside a 32-row flag tile (only at toy sizes, P < 32): re-derive the tile
-        # map of the local rows from the table itself (one-off table preparation, not step arithmetic)
-        key = ("flags_p_loc", r0, r1)
-        if key not in t.__dict__:
-            rows = t.bias_p[r0:r1]
-            pad = torch.nn.functional.pad(rows, (0, (-E) % 32, 0, (-(r1 - r0)) % 32))
-            t.__dict__[key] = (pad.reshape(pad.shape[0] // 32, 32, pad.shape[1] // 32, 32).abs().amax((1, 3)) > 0) \
-                .to(torch.uint8).contiguous()
-        flags_p_loc = t.__dict__[key]
+    flags_p_loc = band_flags_p(t, r0, r1)
     if mloc:
         tp = xp.view(mloc * P, Cc)
         lnp_loc = ops.layernorm(tp, e.ln1.g, e.ln1.b, e.ln1.eps, pe=t.pe_p[r0:r1], out_dtype=e.cdtype)
