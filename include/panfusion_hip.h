@@ -353,7 +353,9 @@ typedef struct {
                           * norm (diffusers ResnetBlock2D.norm1 / norm2, Transformer2DModel.norm; call sites
                           * MVGenModel.py:102-144,174-198,224-277), so that no statistics pass re-reads the tensor:
                           * fp32 [M / R][2][n_out / 2] = (sum, sum of squares) of each column PAIR (2 k, 2 k + 1) over each run of R output rows,
-                          * R = pf_conv_gemm_gn_rows(desc) (> 0: possible for this problem; images are whole runs).
+                          * R = pf_conv_plan.gn_rows of pf_conv_gemm_plan(desc, 1) (> 0: possible for this problem; images are whole runs).
+                          * The caller states the R it sized the buffer for in gn_rows below: a launch whose plan resolves to another
+                          * R fails with PF_ERR_ARG before anything is written.
                           * Consumed by pf_groupnorm_from_partials.  Fixed summation order, no atomics.      */
     int wrap_pad;        /* 0..2: the input is read as if its WIDTH had been padded circularly by wrap_pad columns on both
                           * sides first (pad_pano, utils/pano.py:74-99), in pre-upsampling columns; the zero padding `pad`
@@ -382,6 +384,7 @@ typedef struct {
                           * phase a = 0: {W[0]}, {W[1] + W[2]}; a = 1: {W[0] + W[1]}, {W[2]}; columns alike).  Bias only (no row vector,
                           * residual, GEGLU / pair epilogue; split3 allowed: c0 = 2 x channels per tap), batch 1, h_out / w_out even; wrap_pad 0..1 with crop 2 x wrap_pad is the
                           * panorama's pad 1 / upsample / conv / crop 2.  gn_partial is supported (runs of R LOW-resolution rows).            */
+    int gn_rows;         /* with gn_partial: the rows per moment run R that gn_partial was sized for (pf_conv_plan.gn_rows); else unused */
 } pf_conv_desc;
 
 enum { PF_EPILOGUE_NONE = 0, PF_EPILOGUE_GEGLU = 1, PF_EPILOGUE_SPLIT = 2 };
@@ -399,6 +402,27 @@ int pf_conv_gemm_gn_rows(const pf_conv_desc* desc);
  * queries above it reflects the plan only (workspace assumed available), it validates nothing.  The cuDNN / cuBLAS
  * heuristics behind diffusers Conv2d / Linear are what it stands in for (MVGenModel.py:102-144,174-198,224-277). */
 int pf_conv_gemm_kernel_id(const pf_conv_desc* desc);
+/* The whole plan pf_conv_gemm resolves for a problem: everything that selects a kernel instantiation or sizes a buffer.  The three
+ * queries above are projections of it (workspace_size: the larger workspace_bytes of the plans with and without moments; gn_rows: that of
+ * the plan with moments; kernel_id: the kernel of the plan without). */
+typedef struct {
+    int kernel;          /* 0 the 4-wave 16x16x32 kernel, 1 the persistent 8-wave 16x16x32 kernel, 2 the persistent 32x32x16 kernel */
+    int mrep, nrep;      /* the block's tile is (32 mrep) x (32 nrep) outputs (kernel 0: mrep 2 or 4; 1: 8; 2: 8 x 10)            */
+    int block_rows;      /* output rows of a block: 32 mrep; kernel 1 also runs 128-row blocks, two per CU                         */
+    int waves;           /* wavefronts per block: 4 (kernel 0, 128-row blocks of kernel 1) or 8                                    */
+    int ring_slots;      /* operand stages in LDS: 2, 3 or 4                                                                       */
+    int splits;          /* K slices of the launch (1: not split), each of kb_per_split 64-element K blocks                        */
+    int kb_per_split;
+    int m_split;         /* > 0: rows [0, m_split) run unsplit, then rows [m_split, M) in tail_splits K slices of tail_kb blocks   */
+    int tail_splits, tail_kb;
+    int gn_rows;         /* rows per GroupNorm-moment run R of pf_conv_desc.gn_partial; 0: no moments (not asked for, or the
+                          * kernel serving the problem cannot emit them)                                                           */
+    int n_tickets;       /* arrival counters the split launch of this plan needs in pf_conv_desc.tickets (0: nothing is split)     */
+    size_t workspace_bytes;  /* split-K scratch of exactly this plan (0: nothing is split)                                         */
+} pf_conv_plan;
+/* want_moments: the plan of a launch that passes gn_partial (it may take another kernel than the launch without: one that can emit
+ * them).  Like the queries it assumes the workspace is available and validates nothing; PF_ERR_ARG for a bad descriptor. */
+pf_status pf_conv_gemm_plan(const pf_conv_desc* desc, int want_moments, pf_conv_plan* out);
 /* Diagnostics only: while `device_buffer` (capacity_blocks x 32 uint64) is set, every pf_conv_gemm launch
  * with at most capacity_blocks workgroups records 4 shader-clock stamps per workgroup (entry, first
  * operand tile landed, K loop done, exit; the 8-wave kernel adds per-wave K-loop time split into

@@ -32,7 +32,16 @@ class ConvDesc(C.Structure):
         ("a_bstride", c_long), ("w_bstride", c_long), ("out_bstride", c_long), ("res_bstride", c_long),
         ("epilogue", c_int), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
         ("gn_partial", c_void_p), ("wrap_pad", c_int), ("crop", c_int),
-        ("tickets", c_void_p), ("n_tickets", c_int), ("split3", c_int), ("subpixel", c_int),
+        ("tickets", c_void_p), ("n_tickets", c_int), ("split3", c_int), ("subpixel", c_int), ("gn_rows", c_int),
+    ]
+
+
+class ConvPlan(C.Structure):
+    """pf_conv_plan"""
+    _fields_ = [
+        ("kernel", c_int), ("mrep", c_int), ("nrep", c_int), ("block_rows", c_int), ("waves", c_int), ("ring_slots", c_int),
+        ("splits", c_int), ("kb_per_split", c_int), ("m_split", c_int), ("tail_splits", c_int), ("tail_kb", c_int),
+        ("gn_rows", c_int), ("n_tickets", c_int), ("workspace_bytes", c_size_t),
     ]
 
 
@@ -142,6 +151,7 @@ SIGNATURES = {
     "pf_conv_gemm_workspace_size": (c_size_t, [C.POINTER(ConvDesc)]),
     "pf_conv_gemm_gn_rows": (c_int, [C.POINTER(ConvDesc)]),
     "pf_conv_gemm_kernel_id": (c_int, [C.POINTER(ConvDesc)]),
+    "pf_conv_gemm_plan": (c_int, [C.POINTER(ConvDesc), c_int, C.POINTER(ConvPlan)]),
     "pf_groupnorm_from_partials": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pf_scale_shift_act_pair": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,

@@ -11,5 +11,5 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace pf
 
-extern "C" int pf_version(void) { return 100; }
+extern "C" int pf_version(void) { return 101; }
 extern "C" const char* pf_last_error_string(void) { return pf::g_err; }

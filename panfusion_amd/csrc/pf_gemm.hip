@@ -1332,56 +1332,54 @@ static inline ProfState prof_snapshot() {
     return s ? *s : ProfState{nullptr, 0};
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize of one kernel instantiation, set once per device: `done` is that instantiation's
+// bitmask of the devices it is set on.  The steady-state launch pays a device-id lookup only.
+pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done, const char* what) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ULL << dev : 0;      // (a device past 63 sets it on every launch)
+    if (e == hipSuccess && (done.load(std::memory_order_relaxed) & bit)) return PF_OK;
+    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute failed: %s", what, hipGetErrorString(e)); return PF_ERR_LAUNCH; }
+    done.fetch_or(bit, std::memory_order_relaxed);
+    return PF_OK;
+}
 
-static int tuning(const char* name, int dflt);
+// The launchers below run ONE pass of a plan's kernel: output rows [p.m_begin, p.M) in p.splits K slices (launch_pass combines the slices).
+
 template <typename T, int MREP, int NREP, bool STATS, bool S3, int STAGES>
 static pf_status launch_ring(const GemmParams& p, int batch, hipStream_t st) {
     constexpr int BM = 32 * MREP, BN = 32 * NREP;
     const size_t smem = static_cast<size_t>(STAGES) * (BM + BN) * 64 * sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> lds_set{0};
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES>), smem, lds_set, "pf_conv_gemm");
+    if (s != PF_OK) return s;
     hipLaunchKernelGGL((k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES>), dim3(p.mtiles * p.ntiles, p.splits, batch), dim3(256), smem, st, p);
+    PF_CHECK_LAUNCH("pf_conv_gemm");
     return PF_OK;
 }
 
 template <typename T, int MREP, int NREP, bool STATS = false, bool S3 = false>
-static pf_status launch_s(const GemmParams& gp, int batch, hipStream_t st) {
+static pf_status launch_s(const pf_conv_plan& g, const GemmParams& gp, int batch, hipStream_t st) {
     constexpr int BM = 32 * MREP, BN = 32 * NREP;
     GemmParams p = gp;
     p.mtiles = static_cast<int>(cdiv(p.M - p.m_begin, BM));
     p.ntiles = static_cast<int>(cdiv(p.N, BN));
     const ProfState ps = prof_snapshot();
     p.prof = (ps.buf && static_cast<long>(p.mtiles) * p.ntiles * p.splits * batch <= ps.blocks) ? ps.buf : nullptr;
-    // a grid of at most one block per CU runs the four-slot ring (one block per CU: nothing to share the CU with anyway)
-    static const int deep_max = tuning("PF_GEMM_DEEP_RING", 1) ? tuning("PF_GEMM_DEEP_RING_MAX_BLOCKS", 256) : 0;
-    const long blocks = static_cast<long>(p.mtiles) * p.ntiles * p.splits * batch;
-    // (instantiated for the plain kernels only: the moment / split-precision variants keep the two-slot form -- compile time)
+    // (the four-slot ring is instantiated for the plain kernels only: the plan gives the moment / split-precision variants two slots)
     if constexpr (!STATS && !S3) {
-        if (blocks <= deep_max && p.K / 64 / p.splits >= 3) launch_ring<T, MREP, NREP, false, false, 4>(p, batch, st);
-        else launch_ring<T, MREP, NREP, false, false, 2>(p, batch, st);
-    } else {
-        launch_ring<T, MREP, NREP, STATS, S3, 2>(p, batch, st);
+        if (g.ring_slots == 4) return launch_ring<T, MREP, NREP, false, false, 4>(p, batch, st);
     }
-    PF_CHECK_LAUNCH("pf_conv_gemm");
-    if (p.splits > 1 && !p.tickets) {
-        const long total = static_cast<long>(batch) * (p.M - p.m_begin) * (p.N / 4);
-        hipLaunchKernelGGL((k_splitk_reduce<T>), dim3(cdiv(total, 256)), dim3(256), 0, st, p);
-        PF_CHECK_LAUNCH("pf_conv_gemm (split-K reduce)");
-    }
-    return PF_OK;
+    return launch_ring<T, MREP, NREP, STATS, S3, 2>(p, batch, st);
 }
 
 template <typename T, int MREP, int NREP>
-static pf_status launch(const GemmParams& gp, int batch, hipStream_t st) {
-    if (gp.s3) return gp.gn_partial ? launch_s<T, MREP, NREP, true, true>(gp, batch, st) : launch_s<T, MREP, NREP, false, true>(gp, batch, st);
-    return gp.gn_partial ? launch_s<T, MREP, NREP, true>(gp, batch, st) : launch_s<T, MREP, NREP, false>(gp, batch, st);
+static pf_status launch(const pf_conv_plan& g, const GemmParams& gp, int batch, hipStream_t st) {
+    if (gp.s3) return gp.gn_partial ? launch_s<T, MREP, NREP, true, true>(g, gp, batch, st) : launch_s<T, MREP, NREP, false, true>(g, gp, batch, st);
+    return gp.gn_partial ? launch_s<T, MREP, NREP, true>(g, gp, batch, st) : launch_s<T, MREP, NREP, false>(g, gp, batch, st);
 }
 
-static int tuning(const char* name, int dflt);
 template <typename T, int NREP, int NW, bool STATS = false, bool S3 = false, int BM = 256>
 static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
     constexpr int BN = 32 * NREP, STAGES = BM == 128 ? 2 : 3;
@@ -1397,15 +1395,12 @@ static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
     const ProfState ps = prof_snapshot();
     p.prof = (ps.buf && static_cast<long>(p.mtiles) * p.ntiles * p.splits * batch <= ps.blocks) ? ps.buf : nullptr;
     const size_t smem = static_cast<size_t>(STAGES) * (BM + BN) * 64 * sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_gemm8<T, NREP, NW, STATS, S3, BM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> lds_set{0};
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm8<T, NREP, NW, STATS, S3, BM>), smem, lds_set, "pf_conv_gemm (8-wave)");
+    if (s != PF_OK) return s;
     // persistent over tiles: one block per CU walks tiles b, b + grid, ... (a multiple of 8 keeps a tile on
     // the XCD its id maps to); PF_GEMM8_PERSIST=0 launches one block per tile
-    static const int cap1 = tuning("PF_GEMM8_PERSIST", 256);
+    const int cap1 = gemm_tuning().big_persist;
     const int cap = BM == 128 ? 2 * cap1 : cap1;                  // (two resident 128-row blocks per CU)
     int grid = p.mtiles * p.ntiles;
     if (cap > 0) {
@@ -1415,11 +1410,6 @@ static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
     }
     hipLaunchKernelGGL((k_conv_gemm8<T, NREP, NW, STATS, S3, BM>), dim3(grid, p.splits, batch), dim3(64 * NW), smem, st, p);
     PF_CHECK_LAUNCH("pf_conv_gemm (8-wave)");
-    if (p.splits > 1 && !p.tickets) {
-        const long total = static_cast<long>(batch) * (p.M - p.m_begin) * (p.N / 4);
-        hipLaunchKernelGGL((k_splitk_reduce<T>), dim3(cdiv(total, 256)), dim3(256), 0, st, p);
-        PF_CHECK_LAUNCH("pf_conv_gemm (split-K reduce)");
-    }
     return PF_OK;
 }
 
@@ -1432,255 +1422,32 @@ static pf_status launch8w(const GemmParams& gp, int batch, hipStream_t st) {
     return launch8w_s<T, NREP, NW, false, false, BM>(gp, batch, st);
 }
 
-static int tuning(const char* name, int dflt);
 template <typename T, int NREP>
-static pf_status launch8(const GemmParams& gp, int batch, hipStream_t st, int bm = 256) {
-    if (bm == 128) return launch8w<T, NREP, 4, 128>(gp, batch, st);       // two 128-row blocks per CU (round 5)
-    // NW = 4 (one 128x80 wave per SIMD, accumulators in AGPRs) is implemented and correct but measured slower
-    // (K step 2520 vs 2222 clocks, epilogue 2x): a lone in-order wave exposes every lgkmcnt / vmcnt / barrier wait.
-    // PF_GEMM8_WAVES=4 selects it (A/B: it moves 28 % fewer fragment bytes through the LDS).
-    static const int nw = tuning("PF_GEMM8_WAVES", 8);
-    if (nw == 4 && !gp.s3) return launch8w<T, NREP, 4>(gp, batch, st);       // (the A/B instantiation has no split-precision variant)
+static pf_status launch8(const pf_conv_plan& g, const GemmParams& gp, int batch, hipStream_t st) {
+    if (g.block_rows == 128) return launch8w<T, NREP, 4, 128>(gp, batch, st);       // two 128-row blocks per CU (round 5)
+    if (g.waves == 4) return launch8w<T, NREP, 4>(gp, batch, st);                   // (PF_GEMM8_WAVES=4, see plan_conv_gemm)
     return launch8w<T, NREP, 8>(gp, batch, st);
 }
 
-static int tuning(const char* name, int dflt) {     // A/B switches for benchmarking (read once)
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-// Tile shape + split-K plan of one problem (shared by the launcher and the workspace query).
-struct GemmPlan { int mrep, nrep, splits, kb_per_split; bool big; int m_split; int tail_splits, tail_kb; int bm = 256; };
-static GemmPlan plan_gemm_small(long M, int N, int K, int batch, bool allow_split, bool s3);
-static GemmPlan plan_gemm0(long M, int N, int K, int batch, bool allow_split, bool s3);
-// Which plans of the 8-wave kernel run as 128-row blocks, two per CU (k_conv_gemm8<..., BM_ = 128>): PF_GEMM_BM128 = 0 none,
-// 1 all of them (A/B), 2 (default) the measured rule: the 128-row blocks win where the tile is ramp / epilogue-bound -- short K
-// (K <= PF_GEMM_BM128_MAXK: isolated +7 % at K = 320, +15...22 % at K = 640, +12...16 % at K = 1280; long-K convolutions lose
-// 3-5 % to the shorter DMA look-ahead and the doubled weight traffic, profiles/r5a_gemm_bm128.txt): same-box step A/B 62.06 -> 61.39 /
-// 61.36 ms (profiles/r5b_ab_gemm_bm128.txt).  PF_GEMM_BM128_ONEROUND=1 also takes every problem that is ONE round of 256-row tiles
-// (a CU then runs a single ramp + K loop + epilogue with nothing to overlap -- the per-rank GEMMs of the sharded layouts): measured
-// neutral to slightly slower on the simulated ranks (8 ranks 14.35 -> 14.48 ms, 4 ranks 19.9 -> 20.4), so off.
-static GemmPlan plan_gemm(long M, int N, int K, int batch, bool allow_split, bool s3 = false) {
-    GemmPlan g = plan_gemm0(M, N, K, batch, allow_split, s3);
-    static const int mode = tuning("PF_GEMM_BM128", 2);
-    static const int max_k = tuning("PF_GEMM_BM128_MAXK", 1280);
-    static const int one_round = tuning("PF_GEMM_BM128_ONEROUND", 0);
-    if (!g.big || g.m_split > 0) return g;
-    if (mode == 1) g.bm = 128;
-    else if (mode == 2) {
-        const long tiles256 = cdiv(M, 256) * cdiv(N, 32 * g.nrep) * batch * g.splits;
-        if (K <= max_k || (one_round && tiles256 <= 256)) g.bm = 128;
+// One pass of plan g's kernel over rows [p.m_begin, p.M), then -- split K without arrival counters -- the second kernel that sums the slabs.
+static pf_status launch_pass(const pf_conv_plan& g, GemmParams p, int dtype, int batch, hipStream_t st) {
+    pf_status s = PF_OK;
+    if (g.kernel == 2) {
+        const ProfState ps = prof_snapshot();
+        p.prof = (ps.buf && ps.blocks >= 256) ? ps.buf : nullptr;
+        s = launch_gemm32(p, dtype, batch, st);
+    } else if (g.kernel == 1) {
+        PF_DISPATCH_16(dtype, "pf_conv_gemm", s = g.nrep == 5 ? launch8<T, 5>(g, p, batch, st) : launch8<T, 4>(g, p, batch, st));
+    } else {
+        PF_DISPATCH_16(dtype, "pf_conv_gemm",
+            if (g.nrep == 5) s = g.mrep == 2 ? launch<T, 2, 5>(g, p, batch, st) : launch<T, 4, 5>(g, p, batch, st);
+            else s = g.mrep == 2 ? launch<T, 2, 4>(g, p, batch, st) : launch<T, 4, 4>(g, p, batch, st));
     }
-    return g;
-}
-static GemmPlan plan_gemm0(long M, int N, int K, int batch, bool allow_split, bool s3) {
-    static const int big_min_tiles = tuning("PF_GEMM8_MIN_TILES", 128);   // 0 disables the 8-wave kernel
-    const int nrep = (N % 160 == 0) ? 5 : 4;
-    const long tiles256 = cdiv(M, 256) * cdiv(N, 32 * nrep) * batch;
-    // one 8-wave block per CU: take it only when the tiles fill their rounds of 256 CUs to >= 60 % overall (320
-    // tiles would idle for 37 % of the launch; the 4-wave kernel's 2 blocks per CU degrade more gracefully).
-    // The threshold was flat at the single-GPU sizes in round 2 (17.4-17.5 steps/s from 50 to 95 %) and was set to 60 on the smaller
-    // per-rank GEMMs of 2 / 4 / 8 ranks (tools/sim_rank.py: 37.1 -> 33.9 ms per step at 2 ranks from 88 to 60 %).  Round 6, last sweep
-    // on the final kernels (profiles/r6n_ab_plan_knobs.txt): 30-50 read -0.2 ... -0.5 ms per step on three boxes, cfg 4 -0.9 ms, the
-    // simulated ranks unchanged (half-filled rounds of the panorama's 64 x 128 level and of the 8 x 8 level now take the persistent kernel): 30.
-    const long rounds = cdiv(tiles256, 256);
-    static const int fill_pct = tuning("PF_GEMM8_FILL", 30);
-    const bool filled = tiles256 * 100 >= rounds * 256 * fill_pct;
-    // a badly filled last round of a LONG-K layer (320 tiles of a 16x16-level 3x3 conv = 1.25 rounds) is better spent on a
-    // split-K tail launch than on a second full round: the tail split below goes first when the fill is under
-    // PF_GEMM8_TAIL_FIRST % (same-box A/B on the mixed scheme: 69.7 -> 68.7 ms per step)
-    static const int tail_first_pct = tuning("PF_GEMM8_TAIL_FIRST", 80);
-    static const int big_min_k = tuning("PF_GEMM8_MIN_K", 0);      // A/B: least K for the 8-wave kernel (measured neutral)
-    // Tail split: whole rounds of 256 tiles run unsplit; the tile rows left over (a badly filled last round)
-    // become a second launch whose K range is split so that it fills the chip once more.  320 tiles then
-    // cost 1.25 rounds instead of 2.
-    static const int tail_on = tuning("PF_GEMM_TAIL_SPLIT", 1);
-    GemmPlan tail;
-    bool tail_ok = false;
-    if (big_min_tiles > 0 && tail_on && allow_split && batch == 1 && N % 4 == 0 && tiles256 > 256 && K >= big_min_k && K / 64 >= tuning("PF_GEMM_TAIL_MINKB", 40)) {
-        const long ntl = cdiv(N, 32 * nrep), mt = cdiv(M, 256);
-        const long rows1 = (tiles256 / 256) * 256 / ntl;            // tile rows of the unsplit launch
-        const long tiles2 = (mt - rows1) * ntl;
-        long sp = tiles2 > 0 ? (256 + tiles2 / 2) / tiles2 : 1;
-        if (sp > (K / 64) / 8) sp = (K / 64) / 8;
-        if (rows1 > 0 && tiles2 > 0 && sp >= 2 && rows1 * ntl * 100 >= (tiles256 / 256) * 256 * 90) {
-            tail.big = true; tail.mrep = 8; tail.nrep = nrep; tail.splits = 1; tail.kb_per_split = K / 64;
-            tail.m_split = static_cast<int>(rows1 * 256);
-            tail.tail_kb = static_cast<int>(cdiv(K / 64, sp));
-            tail.tail_splits = static_cast<int>(cdiv(K / 64, tail.tail_kb));
-            tail_ok = true;
-        }
-    }
-    if (tail_ok && tiles256 * 100 < rounds * 256 * tail_first_pct) return tail;
-    if (big_min_tiles > 0 && tiles256 >= big_min_tiles && filled && K >= big_min_k) {
-        GemmPlan g;
-        g.big = true; g.mrep = 8; g.nrep = nrep; g.splits = 1; g.kb_per_split = K / 64; g.m_split = 0;
-        return g;
-    }
-    if (tail_ok) return tail;
-    // long-K layers with few output tiles (the 8x8 level, the panorama's inner levels): 256-row tiles
-    // re-read the weight panel 2-4x less often than the 64-row tiles of the small kernel; split K so
-    // that one round of blocks covers the chip
-    const int nkb_all = K / 64;
-    if (big_min_tiles > 0 && allow_split && N % 4 == 0 && tiles256 >= 32 && tiles256 <= 128 && nkb_all >= 32) {
-        long sp = 256 / tiles256;
-        if (sp > nkb_all / 16) sp = nkb_all / 16;
-        if (sp >= 2) {
-            GemmPlan g;
-            g.big = true; g.mrep = 8; g.nrep = nrep; g.m_split = 0;
-            g.kb_per_split = static_cast<int>(cdiv(nkb_all, sp));
-            g.splits = static_cast<int>(cdiv(nkb_all, g.kb_per_split));
-            return g;
-        }
-    }
-    return plan_gemm_small(M, N, K, batch, allow_split, s3);
-}
-static GemmPlan plan_gemm_small(long M, int N, int K, int batch, bool allow_split, bool s3) {
-    GemmPlan g;
-    g.big = false; g.m_split = 0;
-    // 160-wide N tiles when they divide N exactly (all UNet widths are multiples of 160), 128-wide
-    // otherwise; 64-row M tiles when 128-row tiles would not fill the 256 CUs (2 blocks per CU).
-    g.nrep = (N % 160 == 0) ? 5 : 4;
-    const long ntiles = cdiv(N, 32 * g.nrep);
-    const long tiles128 = cdiv(M, 128) * ntiles * batch;
-    g.mrep = tiles128 < 512 ? 2 : 4;
-    const long tiles = cdiv(M, 32 * g.mrep) * ntiles * batch;
-    const int nkb = K / 64;
-    g.splits = 1;
-    g.kb_per_split = nkb;
-    // split-K when the grid cannot fill the chip and K is long: aim at ~640 blocks, >= 6 K-blocks each
-    static const int split_min_kb = tuning("PF_GEMM_SPLIT_MINKB", 12);   // least K depth (64-blocks) for split-K on the 4-wave kernel
-    // Round 6: a grid of <= 256 blocks runs the four-slot ring, one block per CU (launch_s): there the split aims at ONE round of the chip
-    // (fewer fp32 slabs for the reduce kernel: 128 tiles x 2 K slices instead of x 5) and a K slice may be as short as 4 steps.
-    static const int deep = tuning("PF_GEMM_DEEP_RING", 1);
-    if (deep && !s3 && tiles <= 256) {                               // (the split-precision kernels keep the two-slot ring and its plan)
-        long s = allow_split && N % 4 == 0 && nkb >= split_min_kb ? 256 / tiles : 1;
-        if (s > nkb / 4) s = nkb / 4;
-        if (s > 32) s = 32;
-        if (s > 1) {
-            g.kb_per_split = static_cast<int>(cdiv(nkb, s));
-            g.splits = static_cast<int>(cdiv(nkb, g.kb_per_split));
-        }
-        return g;
-    }
-    if (allow_split && N % 4 == 0 && tiles <= 320 && nkb >= split_min_kb) {
-        long s = (640 + tiles - 1) / tiles;
-        if (s > nkb / 6) s = nkb / 6;
-        if (s > 32) s = 32;
-        if (s > 1) {
-            g.kb_per_split = static_cast<int>(cdiv(nkb, s));
-            g.splits = static_cast<int>(cdiv(nkb, g.kb_per_split));
-        }
-    }
-    return g;
-}
-
-// descriptor -> kernel parameters (no validation here)
-static void params_from_desc(const pf_conv_desc* d, GemmParams& p) {
-    const int c1 = d->a1 ? d->c1 : 0;
-    const int Ctot = d->c0 + c1;
-    p.a0 = static_cast<const unsigned short*>(d->a0);
-    p.a1 = static_cast<const unsigned short*>(d->a1);
-    p.c0 = d->c0; p.c1 = c1; p.a0_ld = d->a0_ld; p.a1_ld = d->a1 ? d->a1_ld : 0;
-    p.h_in = d->h_in; p.w_in = d->w_in; p.h_out = d->h_out; p.w_out = d->w_out;
-    p.ksize = d->ksize; p.stride = d->stride; p.pad = d->pad; p.up = d->upsample;
-    p.wrap = d->wrap_pad; p.crop = d->crop;
-    p.w = static_cast<const unsigned short*>(d->w);
-    p.rows_per_img = d->h_out * d->w_out;
-    p.M = d->n_img * p.rows_per_img; p.N = d->n_out; p.K = d->ksize * d->ksize * Ctot;
-    p.bias = d->bias; p.rowvec = d->rowvec; p.rowvec_ld = d->rowvec_ld;
-    p.residual = d->residual; p.res_ld = d->res_ld;
-    p.res_f32 = d->residual != nullptr && d->res_dtype == PF_F32;
-    p.out = d->out; p.out_ld = d->out_ld; p.out_f32 = d->out_dtype == PF_F32;
-    p.geglu = d->epilogue == PF_EPILOGUE_GEGLU;
-    p.split_out = d->epilogue == PF_EPILOGUE_SPLIT;
-    p.a_bs = d->a_bstride; p.w_bs = d->w_bstride; p.out_bs = d->out_bstride; p.res_bs = d->res_bstride;
-    p.mtiles = p.ntiles = 0;
-    p.prof = nullptr;
-    p.s3 = d->split3 != 0;
-    p.batch = d->batch;
-    p.gn_partial = nullptr; p.gn_rows = 0;
-    p.m_begin = 0; p.splits = 1; p.kb_per_split = 0; p.partial = nullptr; p.tickets = nullptr;
-    p.a0_bytes = p.a1_bytes = p.w_bytes = 0; p.adv_img = p.adv_y = p.adv_x = 0;
-    p.subpix = 0;
-    p.fastseg = (d->upsample == 0 || d->subpixel) && d->wrap_pad == 0 && tuning("PF_CONV_FASTSEG", 1) ? 1 : 0;
-    if (d->subpixel) {
-        // nearest x2 + 3x3 conv == four 2x2 convolutions on the low-resolution grid, one per output phase (blockIdx.z): 4 Cin
-        // instead of 9 Cin MACs per output value.  Everything below is the LOW-resolution problem; out_row() scatters the rows.
-        p.subpix = 1; p.ksize = 2; p.up = 0; p.pad = 0;
-        p.h_out = d->h_out / 2; p.w_out = d->w_out / 2;
-        p.rows_per_img = p.h_out * p.w_out;
-        p.M = d->n_img * p.rows_per_img; p.K = 4 * Ctot;
-        p.crop = d->crop / 2;
-        p.batch = 4; p.a_bs = 0; p.out_bs = 0; p.res_bs = 0; p.w_bs = static_cast<long>(p.N) * p.K;
-    }
-}
-static inline int eff_batch(const pf_conv_desc* d) { return d->subpixel ? 4 : d->batch; }
-
-// Rows per GroupNorm-moment part (pf_conv_desc.gn_partial) of this problem under plan g: the fragment rows of one
-// wavefront -- or 0 where the moments cannot be produced: split K (the reduce kernel writes the output), a batch,
-// images that are not whole parts, or an operand mix that takes the per-fragment (generic) epilogue.
-static int gn_rows_for(const GemmParams& p, const GemmPlan& g, int batch) {
-    if ((batch != 1 && !p.subpix) || g.splits > 1 || g.m_split > 0 || p.geglu || p.split_out) return 0;   // (the four sub-pixel phases of an image are contiguous runs: gn_part)
-    // Layers with a residual are left to the consumer's statistics pass by default.  Round 3: the moment phase has to read the
-    // residual tile a second time, which costs an HBM-bound layer as much as that pass saves (fp32-residual linear at
-    // 163840 x 320: 141 -> 171 us, the pass it replaces 42 us; VAE decode 107 -> 122 ms; profiles/archive/r3d_gemm_gn.txt).  Round 4: fp32
-    // tiles with an fp32 residual form their moments inside the store loop instead (epilogue_f32_stats: no second read, no extra
-    // registers) -- and the step still does not move: 63.17 vs 63.33 / 63.54 ms on one box, 61.23 / 61.40 vs 61.00 on another
-    // (profiles/r4ah_ab_gn_moments_residual.txt): ~30 statistics passes of 10-55 us leave the critical stream, the column-block-major
-    // store order of the fused epilogue gives as much back.  Off; PF_GN_EPILOGUE_RES=1 enables it (tests run both).
-    // Without a residual (resnet conv1 -> norm2, the up-sampling conv) the phase costs 2-3 us against a 25-40 us pass.
-    if (p.residual && tuning("PF_GN_EPILOGUE_RES", 0) == 0) return 0;
-    if (g.big && tuning("PF_GEMM8_WAVES", 8) == 4) return 0;       // (the one-wave-per-SIMD A/B instantiation has no moment variant)
-    const int rows = g.big ? 64 : 16 * g.mrep;
-    const int BM = g.big ? 256 : 32 * g.mrep;
-    if (p.rows_per_img % rows != 0 || p.N % (32 * g.nrep) != 0) return 0;      // whole runs per image, whole N tiles
-    if (p.out_f32) {
-        const bool ok = !p.rowvec && (p.out_ld & 3) == 0 && (!p.residual || (p.res_f32 && (p.res_ld & 3) == 0));
-        return ok ? rows : 0;
-    }
-    const bool staged = !p.res_f32 && (p.out_ld & 7) == 0 && (p.N & 7) == 0 && !(p.rowvec && p.residual) &&
-                        !(p.rowvec && p.rows_per_img < BM);
-    return staged ? rows : 0;
-}
-
-
-// Which problems take the 32x32x16 kernel of pf_gemm32.hip (256 x 320 tiles, one persistent block per CU): plain (not split-precision)
-// layers with N a multiple of 320 and a long K whose tiles fill whole rounds of 256 CUs -- or whole rounds plus a tail that a split-K
-// launch spreads over the chip once more (640 tiles = 2 rounds + 128 tiles x 2 K slices; 320 = 1 round + 64 x 4).  OFF by default
-// (PF_GEMM32=1 enables it; PF_GEMM32_MINK is the least K, PF_GEMM32_K1=1 also admits 1x1 layers): its K loop needs 1680 clocks per 32-wide
-// stage against the 16x16 kernel's 2140 per equal-FLOP step, and on N(0,1) operands it is no faster -- the chip is POWER capped there
-// (zero operands: +7 %), v_mfma_f32_32x32x16 draws ~13 % more per FLOP than v_mfma_f32_16x16x32 on random data, and the step is 0.6 ms
-// slower with it because of the split-K tails its 2.5 / 1.25 rounds need (profiles/r6_gemm32_power_cap.txt).
-struct Plan32 { bool use; int m_split, tail_splits, tail_kb; };
-static Plan32 plan32(const GemmParams& p, int batch, bool allow_split) {
-    Plan32 r{false, 0, 0, 0};
-    static const int min_k = tuning("PF_GEMM32_MINK", 2560), k1 = tuning("PF_GEMM32_K1", 0);
-    const int on = tuning("PF_GEMM32", 0);                         // (read per call: the tests switch it on for their own launches)
-    if (!on || p.s3 || p.subpix || batch != 1 || p.N % 320 != 0 || p.K < min_k || p.K % 64 != 0 || p.geglu) return r;
-    if (p.ksize != 3 && !k1) return r;
-    const long ntl = p.N / 320, mt = cdiv(p.M, 256), tiles = mt * ntl;
-    const long full = tiles / 256 * 256, rest = tiles - full;
-    if (rest == 0) { r.use = true; return r; }
-    if (full == 0 || !allow_split || p.N % 4 != 0) return r;
-    const long rows1 = full / ntl;                                  // tile rows of the unsplit launch (ntl divides 256)
-    long sp = (256 + rest / 2) / rest;
-    const int nkb = p.K / 64;
-    if (sp > nkb / 8) sp = nkb / 8;
-    if (sp < 2 || rest * sp > 256) return r;
-    r.use = true;
-    r.m_split = static_cast<int>(rows1 * 256);
-    r.tail_kb = static_cast<int>(cdiv(nkb, sp));
-    r.tail_splits = static_cast<int>(cdiv(nkb, r.tail_kb));
-    return r;
-}
-// Rows per GroupNorm-moment run of the 32x32 kernel (a wave's 64 rows), or 0: a split-K tail (the reduce kernel writes those rows), a
-// residual (left to the consumer's pass, see gn_rows_for), a row vector over images that are not whole runs, pair output.
-static int gn_rows32(const GemmParams& p, const Plan32& g) {
-    if (!g.use || g.m_split > 0 || p.residual || p.split_out || p.geglu) return 0;
-    if (p.rows_per_img % 64 != 0) return 0;
-    const bool ok = p.out_f32 ? (p.out_ld & 3) == 0 : (p.out_ld & 7) == 0;
-    return ok ? 64 : 0;
+    if (s != PF_OK || p.splits == 1 || p.tickets) return s;
+    const long total = static_cast<long>(batch) * (p.M - p.m_begin) * (p.N / 4);
+    PF_DISPATCH_16(dtype, "pf_conv_gemm", hipLaunchKernelGGL((k_splitk_reduce<T>), dim3(cdiv(total, 256)), dim3(256), 0, st, p));
+    PF_CHECK_LAUNCH("pf_conv_gemm (split-K reduce)");
+    return PF_OK;
 }
 
 }  // namespace pf
@@ -1694,7 +1461,6 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     PF_REQUIRE(d->out_dtype == d->dtype || d->out_dtype == PF_F32, "pf_conv_gemm: out_dtype must equal dtype or be PF_F32");
     PF_REQUIRE(!d->residual || d->res_dtype == d->dtype || d->res_dtype == PF_F32, "pf_conv_gemm: res_dtype must equal dtype or be PF_F32");
     const int c1 = d->a1 ? d->c1 : 0;
-    const int Ctot = d->c0 + c1;
     PF_REQUIRE(d->c0 > 0 && d->c0 % 64 == 0 && c1 % 64 == 0, "pf_conv_gemm: channel counts (%d,%d) must be multiples of 64", d->c0, c1);
     PF_REQUIRE(d->ksize == 1 || d->ksize == 3, "pf_conv_gemm: ksize must be 1 or 3");
     PF_REQUIRE(d->stride == 1 || d->stride == 2, "pf_conv_gemm: stride must be 1 or 2");
@@ -1740,54 +1506,20 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
         PF_REQUIRE(d->ksize == 3 && d->upsample == 1 && d->stride == 1 && d->pad == 1 && d->batch == 1 && !d->residual && !d->rowvec &&
                    d->epilogue == PF_EPILOGUE_NONE && d->h_out % 2 == 0 && d->w_out % 2 == 0 && d->crop % 2 == 0 && d->wrap_pad <= 1,
                    "pf_conv_gemm: subpixel serves nearest x2 + 3x3 stride-1 pad-1 convolutions (bias only; weights packed [4][n_out][2][2][c0 + c1])");
-    const int batch = eff_batch(d);
+    const int batch = d->subpixel ? 4 : d->batch;
     GemmParams p;
     params_from_desc(d, p);
-    Plan32 g32 = plan32(p, batch, d->workspace != nullptr);
-    if (g32.use && d->gn_partial && gn_rows32(p, g32) == 0) g32.use = false;     // (moments asked for: the plan that can emit them)
-    if (g32.use) {
-        if (d->gn_partial) {
-            PF_REQUIRE(aligned16(d->gn_partial), "pf_conv_gemm: gn_partial must be 16-byte aligned");
-            p.gn_partial = d->gn_partial;
-            p.gn_rows = 64;
-        }
-        const long npix = static_cast<long>(d->n_img) * d->h_in * d->w_in;
-        const long a0b = ((npix - 1) * p.a0_ld + p.c0) * 2, a1b = p.a1 ? ((npix - 1) * p.a1_ld + p.c1) * 2 : 0;
-        const long wb = static_cast<long>(p.N) * p.K * 2;
-        PF_REQUIRE(a0b < (1L << 31) && a1b < (1L << 31) && wb < (1L << 31),
-                   "pf_conv_gemm: each operand must be smaller than 2 GiB (32-bit buffer offsets)");
-        p.a0_bytes = static_cast<unsigned>(a0b); p.a1_bytes = static_cast<unsigned>(a1b); p.w_bytes = static_cast<unsigned>(wb);
-        p.splits = 1; p.kb_per_split = p.K / 64;
-        {
-            const ProfState ps = prof_snapshot();
-            p.prof = (ps.buf && ps.blocks >= 256) ? ps.buf : nullptr;
-        }
-        hipStream_t st32 = as_stream(stream);
-        if (g32.m_split == 0) return launch_gemm32(p, d->dtype, 1, st32);
-        const size_t need = static_cast<size_t>(g32.tail_splits) * (p.M - g32.m_split) * p.N * sizeof(float);
-        PF_REQUIRE(d->workspace_bytes >= need && aligned16(d->workspace),
-                   "pf_conv_gemm: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, d->workspace_bytes);
-        GemmParams p1 = p, p2 = p;
-        p1.M = g32.m_split;
-        p2.m_begin = g32.m_split; p2.splits = g32.tail_splits; p2.kb_per_split = g32.tail_kb;
-        p2.partial = static_cast<float*>(d->workspace);
-        pf_status s1 = launch_gemm32(p1, d->dtype, 1, st32);
-        if (s1 != PF_OK) return s1;
-        s1 = launch_gemm32(p2, d->dtype, 1, st32);
-        if (s1 != PF_OK) return s1;
-        const long total = static_cast<long>(p2.M - p2.m_begin) * (p2.N / 4);
-        PF_DISPATCH_16(d->dtype, "pf_conv_gemm", hipLaunchKernelGGL((k_splitk_reduce<T>), dim3(cdiv(total, 256)), dim3(256), 0, st32, p2));
-        PF_CHECK_LAUNCH("pf_conv_gemm (split-K reduce)");
-        return PF_OK;
-    }
-    GemmPlan g = plan_gemm(p.M, p.N, p.K, batch, d->workspace != nullptr, p.s3 != 0);
+    const pf_conv_plan g = plan_conv_gemm(p, batch, d->workspace != nullptr, d->gn_partial != nullptr);
     if (d->gn_partial) {
-        const int r = gn_rows_for(p, g, batch);
-        PF_REQUIRE(r > 0 && aligned16(d->gn_partial), "pf_conv_gemm: gn_partial given but this problem cannot emit GroupNorm moments (ask pf_conv_gemm_gn_rows first)");
+        PF_REQUIRE(g.gn_rows > 0, "pf_conv_gemm: gn_partial given but this problem cannot emit GroupNorm moments (ask pf_conv_gemm_gn_rows first)");
+        PF_REQUIRE(aligned16(d->gn_partial), "pf_conv_gemm: gn_partial must be 16-byte aligned");
+        // (a caller that cached a plan made under other PF_GEMM32 / PF_GN_EPILOGUE_RES settings: its buffer has the wrong number of runs)
+        PF_REQUIRE(d->gn_rows == g.gn_rows, "pf_conv_gemm: gn_partial is sized for runs of gn_rows = %d rows, but this launch's plan writes runs of %d rows (ask pf_conv_gemm_plan again)",
+                   d->gn_rows, g.gn_rows);
         p.gn_partial = d->gn_partial;
-        p.gn_rows = r;
+        p.gn_rows = g.gn_rows;
     }
-    {   // extents for the buffer descriptors of the 8-wave kernel (32-bit offsets, < 2 GiB)
+    {   // extents for the buffer descriptors of the 8-wave and 32x32 kernels (32-bit offsets, < 2 GiB)
         const long npix = static_cast<long>(d->n_img) * d->h_in * d->w_in;
         const long a0b = ((npix - 1) * p.a0_ld + p.c0) * 2, a1b = p.a1 ? ((npix - 1) * p.a1_ld + p.c1) * 2 : 0;
         const long wb = static_cast<long>(p.N) * p.K * 2;      // (per batch element / sub-pixel phase: the kernels offset the base by w_bs)
@@ -1795,50 +1527,30 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
                    "pf_conv_gemm: each operand must be smaller than 2 GiB (32-bit buffer offsets)");
         p.a0_bytes = static_cast<unsigned>(a0b); p.a1_bytes = static_cast<unsigned>(a1b); p.w_bytes = static_cast<unsigned>(wb);
     }
-    p.splits = g.splits; p.kb_per_split = g.kb_per_split;
     p.partial = static_cast<float*>(d->workspace);
     // In-launch combine: implemented, bit-identical (tests/test_gpu_kernels.py), and OFF by default -- it does not pay at these
     // tile sizes: the last-arriving workgroup reads splits x 164 KB of slabs through one CU (~65 GB/s per block cross-XCD,
     // MI355X_MICROARCH.md "handoff-payload") while the second kernel spreads the same reads over the whole chip: the step went
     // 65.3 -> 67.8 ms with write-through slabs, -> 72.9 ms with a release fence per workgroup (profiles/archive/r3k_ab_splitk.txt,
-    // r3l_ab_splitk.txt).  PF_SPLITK_INKERNEL=1 enables it for A/B.
-    if (d->tickets && tuning("PF_SPLITK_INKERNEL", 0) && d->workspace_bytes < (1ULL << 32)) {      // (32-bit slab offsets)
+    // r3l_ab_splitk.txt).  PF_SPLITK_INKERNEL=1 enables it for A/B (16x16x32 kernels only).
+    if (d->tickets && g.kernel != 2 && gemm_tuning().splitk_inkernel && d->workspace_bytes < (1ULL << 32)) {      // (32-bit slab offsets)
         // enough zeroed counters for every (batch, tile) of the split launch?  (tile counts of split plans: <= 320 of the
         // 4-wave kernel, <= 255 of the 8-wave one)
-        const int bm = g.big ? g.bm : 32 * g.mrep, bn = 32 * g.nrep;
-        const long rows = g.big && g.m_split > 0 ? p.M - g.m_split : p.M;
-        const long need = cdiv(rows, bm) * cdiv(p.N, bn) * batch;
-        PF_REQUIRE(d->n_tickets >= need && (reinterpret_cast<uintptr_t>(d->tickets) & 3) == 0,
-                   "pf_conv_gemm: %ld arrival counters needed, %d given", need, d->n_tickets);
+        PF_REQUIRE(d->n_tickets >= g.n_tickets && (reinterpret_cast<uintptr_t>(d->tickets) & 3) == 0,
+                   "pf_conv_gemm: %d arrival counters needed, %d given", g.n_tickets, d->n_tickets);
         p.tickets = d->tickets;
     }
-    p.m_begin = 0;
+    PF_REQUIRE(g.workspace_bytes == 0 || (d->workspace_bytes >= g.workspace_bytes && aligned16(d->workspace)),
+               "pf_conv_gemm: workspace of %zu bytes (16-byte aligned) needed, got %zu", g.workspace_bytes, d->workspace_bytes);
     hipStream_t st = as_stream(stream);
-    if (g.big && g.m_split > 0) {           // two launches: full rounds unsplit, then the tail rows with split K
-        const size_t need = static_cast<size_t>(g.tail_splits) * (p.M - g.m_split) * p.N * sizeof(float);
-        PF_REQUIRE(d->workspace_bytes >= need && aligned16(d->workspace),
-                   "pf_conv_gemm: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, d->workspace_bytes);
-        GemmParams p1 = p, p2 = p;
-        p1.M = g.m_split; p1.splits = 1; p1.kb_per_split = p.K / 64;
-        p2.m_begin = g.m_split; p2.splits = g.tail_splits; p2.kb_per_split = g.tail_kb;
-        PF_DISPATCH_16(d->dtype, "pf_conv_gemm",
-            if (g.nrep == 5) { pf_status s1 = launch8<T, 5>(p1, 1, st, g.bm); if (s1 != PF_OK) return s1; return launch8<T, 5>(p2, 1, st, g.bm); }
-            else { pf_status s1 = launch8<T, 4>(p1, 1, st, g.bm); if (s1 != PF_OK) return s1; return launch8<T, 4>(p2, 1, st, g.bm); });
-    }
-    if (p.splits > 1) {
-        const size_t need = static_cast<size_t>(p.splits) * batch * p.M * p.N * sizeof(float);
-        PF_REQUIRE(d->workspace_bytes >= need && aligned16(d->workspace),
-                   "pf_conv_gemm: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, d->workspace_bytes);
-    }
-    if (g.big) {
-        PF_DISPATCH_16(d->dtype, "pf_conv_gemm",
-            if (g.nrep == 5) return launch8<T, 5>(p, batch, st, g.bm);
-            else return launch8<T, 4>(p, batch, st, g.bm));
-    }
-    PF_DISPATCH_16(d->dtype, "pf_conv_gemm",
-        if (g.nrep == 5) return g.mrep == 2 ? launch<T, 2, 5>(p, batch, st) : launch<T, 4, 5>(p, batch, st);
-        else return g.mrep == 2 ? launch<T, 2, 4>(p, batch, st) : launch<T, 4, 4>(p, batch, st));
-    return PF_OK;
+    p.splits = g.splits; p.kb_per_split = g.kb_per_split;
+    if (g.m_split == 0) return launch_pass(g, p, d->dtype, batch, st);
+    // two launches: full rounds unsplit, then the tail rows with split K
+    GemmParams p2 = p;
+    p.M = g.m_split;
+    p2.m_begin = g.m_split; p2.splits = g.tail_splits; p2.kb_per_split = g.tail_kb;
+    const pf_status s1 = launch_pass(g, p, d->dtype, batch, st);
+    return s1 != PF_OK ? s1 : launch_pass(g, p2, d->dtype, batch, st);
 }
 
 extern "C" pf_status pf_debug_gemm_profile(void* device_buffer, long capacity_blocks) {
@@ -1846,54 +1558,4 @@ extern "C" pf_status pf_debug_gemm_profile(void* device_buffer, long capacity_bl
     const ProfState* s = device_buffer ? new ProfState{static_cast<unsigned long long*>(device_buffer), capacity_blocks} : nullptr;
     g_prof_state.store(s, std::memory_order_release);
     return PF_OK;
-}
-
-extern "C" int pf_conv_gemm_gn_rows(const pf_conv_desc* d) {
-    if (!d || d->batch < 1 || d->n_out < 1 || d->n_img < 1) return 0;
-    GemmParams p;
-    params_from_desc(d, p);
-    if (d->subpixel) return gn_rows_for(p, plan_gemm(p.M, p.N, p.K, 4, true, p.s3 != 0), 4);
-    {
-        const Plan32 g32 = plan32(p, d->batch, true);
-        if (g32.use) {
-            const int r = gn_rows32(p, g32);
-            if (r > 0) return r;                                    // else: the 16x16 kernels' plan below serves a launch that asks for moments
-        }
-    }
-    return gn_rows_for(p, plan_gemm(p.M, p.N, p.K, d->batch, true, p.s3 != 0), d->batch);
-}
-
-extern "C" int pf_conv_gemm_kernel_id(const pf_conv_desc* d) {
-    if (!d || d->batch < 1 || d->n_out < 1 || d->n_img < 1) return -1;
-    GemmParams p;
-    params_from_desc(d, p);
-    if (plan32(p, eff_batch(d), true).use) return 2;
-    return plan_gemm(p.M, p.N, p.K, eff_batch(d), true, p.s3 != 0).big ? 1 : 0;
-}
-
-extern "C" size_t pf_conv_gemm_workspace_size(const pf_conv_desc* d) {
-    if (!d || d->batch < 1 || d->n_out < 1) return 0;
-    const int c1 = d->a1 ? d->c1 : 0;
-    if (d->subpixel) {                                              // the four phase problems on the low-resolution grid (params_from_desc)
-        GemmParams p;
-        params_from_desc(d, p);
-        const GemmPlan g = plan_gemm(p.M, p.N, p.K, 4, true, p.s3 != 0);
-        return g.splits > 1 ? static_cast<size_t>(g.splits) * 4 * p.M * p.N * sizeof(float) : 0;
-    }
-    const long M = static_cast<long>(d->n_img) * d->h_out * d->w_out;
-    const int K = d->ksize * d->ksize * (d->c0 + c1);
-    size_t need32 = 0;
-    {
-        GemmParams p;
-        params_from_desc(d, p);
-        const Plan32 g32 = plan32(p, d->batch, true);
-        if (g32.use) {
-            need32 = g32.m_split > 0 ? static_cast<size_t>(g32.tail_splits) * (M - g32.m_split) * d->n_out * sizeof(float) : 0;
-            if (gn_rows32(p, g32) > 0 || p.residual) return need32;      // (no launch of this problem falls back to the 16x16 plan)
-        }
-    }
-    // (a launch that asks for GroupNorm moments the 32x32 plan cannot emit takes the 16x16 plan: room for either)
-    const GemmPlan g = plan_gemm(M, d->n_out, K, d->batch, true, d->split3 != 0);
-    if (g.big && g.m_split > 0) return std::max(need32, static_cast<size_t>(g.tail_splits) * (M - g.m_split) * d->n_out * sizeof(float));
-    return std::max(need32, g.splits > 1 ? static_cast<size_t>(g.splits) * d->batch * M * d->n_out * sizeof(float) : static_cast<size_t>(0));
 }

@@ -604,11 +604,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_gemm32(const GemmParams p) {
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 
-static int tuning32(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 template <typename T, bool STATS>
 static pf_status launch32_s(const GemmParams& gp, int batch, hipStream_t st) {
     using namespace g32;
@@ -622,14 +617,10 @@ static pf_status launch32_s(const GemmParams& gp, int batch, hipStream_t st) {
         p.adv_x = rem % p.w_out;
     }
     const size_t smem = static_cast<size_t>(SLOTS) * STAGE * sizeof(unsigned short);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_gemm32<T, STATS>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-        if (e != hipSuccess) { set_error("pf_conv_gemm (32x32): hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return PF_ERR_LAUNCH; }
-        attr_set = true;
-    }
-    static const int cap = tuning32("PF_GEMM32_PERSIST", 256);
+    static std::atomic<unsigned long long> lds_set{0};
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm32<T, STATS>), smem, lds_set, "pf_conv_gemm (32x32)");
+    if (s != PF_OK) return s;
+    const int cap = gemm_tuning().gemm32_persist;
     int grid = p.mtiles * p.ntiles;
     if (cap > 0) {
         int gx = std::max(1, cap / (p.splits * batch));

@@ -1,6 +1,9 @@
 // Shared by the tile GEMM kernels (pf_gemm.hip: 16x16x32 MFMA tiles; pf_gemm32.hip: 32x32x16 MFMA tiles): kernel parameters, phase stamps,
 // the per-quad generic epilogue and the split-K slab store.
 #pragma once
+#include <atomic>
+#include <cstdlib>
+
 #include "pf_common.h"
 
 namespace pf {
@@ -160,5 +163,47 @@ __device__ __forceinline__ void slab_store(const GemmParams& p, long elem, const
 
 // pf_gemm32.hip: the 32x32x16-MFMA tile kernel (256 x 320 block) on output rows [m_begin, M); split-K slabs are combined by the caller
 pf_status launch_gemm32(const GemmParams& gp, int dtype, int batch, hipStream_t st);
+
+// ---- host side: knobs and the plan of a problem (pf_gemm_plan.hip) ------------------------------------------------------------------
+
+// Every environment knob of the tile GEMMs (A/B switches for benchmarking) with its default.  The members are read ONCE per process
+// (gemm_tuning()); the three that tests switch inside a process are the static accessors below them, read on every call.
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+struct GemmTuning {
+    int deep_ring = env_int("PF_GEMM_DEEP_RING", 1);            // 4-wave grids of at most deep_ring_max_blocks blocks run the four-slot ring, one block per CU
+    int deep_ring_max_blocks = env_int("PF_GEMM_DEEP_RING_MAX_BLOCKS", 256);
+    int split_min_kb = env_int("PF_GEMM_SPLIT_MINKB", 12);      // least K depth (64-blocks) for split-K on the 4-wave kernel
+    int big_min_tiles = env_int("PF_GEMM8_MIN_TILES", 128);     // least 256-row tiles for the 8-wave kernel; 0 disables it
+    int big_fill_pct = env_int("PF_GEMM8_FILL", 30);            // least fill (%) of the rounds of 256 CUs for the 8-wave kernel
+    int big_min_k = env_int("PF_GEMM8_MIN_K", 0);               // least K for the 8-wave kernel (measured neutral)
+    int big_waves = env_int("PF_GEMM8_WAVES", 8);               // 4 = the one-wave-per-SIMD instantiation of the 256-row blocks
+    int big_persist = env_int("PF_GEMM8_PERSIST", 256);         // resident blocks of the persistent 8-wave grid; 0 = one block per tile
+    int tail_split = env_int("PF_GEMM_TAIL_SPLIT", 1);          // a badly filled last round of the 8-wave kernel becomes a split-K tail launch
+    int tail_first_pct = env_int("PF_GEMM8_TAIL_FIRST", 80);    // the tail split goes first when the rounds are filled to less than this (%)
+    int tail_min_kb = env_int("PF_GEMM_TAIL_MINKB", 40);        // least K depth (64-blocks) for a tail split
+    int bm128 = env_int("PF_GEMM_BM128", 2);                    // 8-wave plans as 128-row blocks, two per CU: 0 none, 1 all, 2 the measured rule
+    int bm128_max_k = env_int("PF_GEMM_BM128_MAXK", 1280);      // rule 2 takes K up to this
+    int bm128_one_round = env_int("PF_GEMM_BM128_ONEROUND", 0); // rule 2 also takes problems that are one round of 256-row tiles
+    int gemm32_min_k = env_int("PF_GEMM32_MINK", 2560);         // least K for the 32x32x16 kernel
+    int gemm32_k1 = env_int("PF_GEMM32_K1", 0);                 // 1 also admits 1x1 layers to the 32x32x16 kernel
+    int gemm32_persist = env_int("PF_GEMM32_PERSIST", 256);     // resident blocks of the persistent 32x32x16 grid; 0 = one block per tile
+    int splitk_inkernel = env_int("PF_SPLITK_INKERNEL", 0);     // 1 = the last-arriving workgroup combines the split-K slabs (pf_conv_desc.tickets)
+    // read on every call:
+    static int gemm32() { return env_int("PF_GEMM32", 0); }                      // 1 enables the 32x32x16 kernel
+    static int gn_epilogue_res() { return env_int("PF_GN_EPILOGUE_RES", 0); }    // 1 = layers with a residual emit GroupNorm moments too
+    static int conv_fastseg() { return env_int("PF_CONV_FASTSEG", 1); }          // 0 = the general segment arithmetic everywhere (GemmParams.fastseg)
+};
+const GemmTuning& gemm_tuning();
+
+// descriptor -> kernel parameters (no validation here)
+void params_from_desc(const pf_conv_desc* d, GemmParams& p);
+// THE plan of a problem: what pf_conv_gemm launches and every query reports.  batch: 4 for the sub-pixel phases, else pf_conv_desc.batch;
+// allow_split: split-K scratch is at hand; want_moments: the launch passes pf_conv_desc.gn_partial.
+pf_conv_plan plan_conv_gemm(const GemmParams& p, int batch, bool allow_split, bool want_moments);
+// pf_gemm.hip: lets `kernel` take `bytes` of dynamic LDS on the current device; `done` is that kernel instantiation's own record
+pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done, const char* what);
 
 }  // namespace pf

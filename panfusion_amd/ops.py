@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, ConvDesc, LinearWsDesc, check
+from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, ConvDesc, ConvPlan, LinearWsDesc, check
 
 _DT = {torch.bfloat16: PF_BF16, torch.float16: PF_F16, torch.float32: PF_F32}
 
@@ -21,7 +21,9 @@ TRACE = None
 
 
 class _PlanCache(__import__("threading").local):
-    """conv_gemm: problem shape -> [split-K scratch bytes, GroupNorm-moment rows, descriptor] as the library plans it.  Per host
+    """conv_gemm: problem shape -> [descriptor, plan without GroupNorm moments, plan with (asked on first use)] as the library plans it
+    (pf_conv_gemm_plan).  The plans hold the live knobs PF_GEMM32 / PF_GN_EPILOGUE_RES as they were when asked: clear this cache after
+    switching one (a moment launch on a stale plan is refused by the library: pf_conv_desc.gn_rows).  Per host
     THREAD (the cached descriptor's pointer members are rewritten on every call: two threads issuing the same shape must not
     share one) and bounded (variable batch sizes / resolutions: the oldest shape goes first)."""
     LIMIT = 4096
@@ -590,56 +592,45 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     out_ld = out_ld if out_ld is not None else _ld(out)
     epilogue = 1 if geglu else (2 if split_out else 0)
     # One descriptor per problem SHAPE, filled once and reused (a launch-bound training step issues ~1500 of these per step:
-    # the ~35 scalar members cost more host time than the call); with it the library's plan for the shape (split-K scratch,
-    # GroupNorm-moment rows), asked once.  Per call only the pointers change.
+    # the ~35 scalar members cost more host time than the call); with it the library's plans for the shape, asked once.  Per call
+    # only the pointers change.
     pkey = (c0, c1, a0_ld, a1_ld, n_img, h_in, w_in, h_out, w_out, ksize, stride, pad, upsample, n_out, batch, epilogue, wrap_pad,
             crop, dt(a0), dt(out_dtype), residual is not None, res_dtype, res_ld, rowvec is not None, rowvec_ld, bias is not None,
             out_ld, a_bstride, w_bstride, out_bstride, res_bstride, bool(split3), bool(subpixel))
     plans = _PLANS.plans
     plan = plans.get(pkey)
     if plan is None:
-        d = ConvDesc()
-        d.c0, d.c1, d.a0_ld, d.a1_ld = c0, c1, a0_ld, a1_ld
-        d.n_img, d.h_in, d.w_in, d.h_out, d.w_out = n_img, h_in, w_in, h_out, w_out
-        d.ksize, d.stride, d.pad, d.upsample = ksize, stride, pad, upsample
-        d.n_out, d.rowvec_ld, d.res_ld, d.res_dtype, d.out_ld = n_out, rowvec_ld, res_ld, res_dtype, out_ld
-        d.out_dtype, d.dtype = dt(out_dtype), dt(a0)
-        d.batch = batch
-        d.a_bstride, d.w_bstride, d.out_bstride, d.res_bstride = a_bstride, w_bstride, out_bstride, res_bstride
-        d.epilogue = epilogue
-        d.wrap_pad, d.crop = wrap_pad, crop
-        d.split3 = int(bool(split3))
-        d.subpixel = int(bool(subpixel))
+        d = _conv_desc(pkey)
         d.a0, d.a1, d.w, d.bias, d.rowvec, d.residual, d.out = _p(a0), _p(a1), _p(w), _p(bias), _p(rowvec), _p(residual), _p(out)
         if len(plans) >= _PLANS.LIMIT:
             plans.pop(next(iter(plans)))
-        plan = plans[pkey] = [_lib.lib().pf_conv_gemm_workspace_size(C.byref(d)), None, d, _lib.lib().pf_conv_gemm_kernel_id(C.byref(d))]
-    d = plan[2]
+        plan = plans[pkey] = [d, _conv_plan(d, 0), None]
+    d = plan[0]
     if plan_only:
-        return plan[3]
+        return plan[1].kernel
     d.a0, d.a1, d.w, d.bias, d.rowvec, d.residual, d.out = _p(a0), _p(a1), _p(w), _p(bias), _p(rowvec), _p(residual), _p(out)
-    d.gn_partial, d.tickets, d.n_tickets = None, None, 0
-    nbytes = plan[0]
+    d.gn_partial, d.gn_rows, d.tickets, d.n_tickets = None, 0, None, 0
+    g, gn = plan[1], None
+    if gn_stats and GN_FROM_EPILOGUE and batch == 1:
+        if plan[2] is None:
+            plan[2] = _conv_plan(d, 1)
+        if plan[2].gn_rows > 0:                # (else: a launch without moments, on the plan without)
+            g = plan[2]
+            gn = (torch.empty(M // g.gn_rows, 2, n_out // 2, device=a0.device, dtype=torch.float32), g.gn_rows)
+            d.gn_partial, d.gn_rows = _p(gn[0]), g.gn_rows
+    nbytes = g.workspace_bytes
     ws = torch.empty(nbytes, device=a0.device, dtype=torch.uint8) if nbytes else None   # split-K slabs
     d.workspace, d.workspace_bytes = _p(ws), nbytes
     if nbytes and SPLITK_INKERNEL:
         # a split-K plan, combined inside the launch by the last-arriving workgroup (off by default: it does not pay at these
         # tile sizes, DESIGN.md 11.4 -- and without it no counter ring has to exist before a graph capture)
         d.tickets, d.n_tickets = _ticket_slice(a0.device), _TICKET_SLICE
-    gn = None
-    if gn_stats and GN_FROM_EPILOGUE and batch == 1:
-        if plan[1] is None:
-            plan[1] = _lib.lib().pf_conv_gemm_gn_rows(C.byref(d))
-        rows = plan[1]
-        if rows > 0:
-            gn = (torch.empty(M // rows, 2, n_out // 2, device=a0.device, dtype=torch.float32), rows)
-            d.gn_partial = _p(gn[0])
     if TRACE is None:
         check(_lib.lib().pf_conv_gemm(C.byref(d), _stream()), "pf_conv_gemm")
     else:
         _traced("k_conv_gemm", 2.0 * M * n_out * (algo_k or ksize * ksize * (c0 + c1)) * batch,
                 lambda: check(_lib.lib().pf_conv_gemm(C.byref(d), _stream()), "pf_conv_gemm"),
-                "M%d N%d K%d k%d s%d u%d b%d%s" % (M, n_out, ksize * ksize * (c0 + c1), ksize, stride, upsample, batch, " g32" if plan[3] == 2 else " subpixel" if subpixel else ""))
+                "M%d N%d K%d k%d s%d u%d b%d%s" % (M, n_out, ksize * ksize * (c0 + c1), ksize, stride, upsample, batch, " g32" if plan[1].kernel == 2 else " subpixel" if subpixel else ""))
     if gn is not None:
         out._pf_gn = gn                      # (a tensor that carries moments must not be written in place afterwards)
     elif hasattr(out, "_pf_gn"):
@@ -647,19 +638,35 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     return out
 
 
+def _conv_desc(pkey):
+    """The scalar members of a pf_conv_desc from conv_gemm's problem key (the pointers are the caller's)."""
+    d = ConvDesc()
+    (d.c0, d.c1, d.a0_ld, d.a1_ld, d.n_img, d.h_in, d.w_in, d.h_out, d.w_out, d.ksize, d.stride, d.pad, d.upsample, d.n_out, d.batch,
+     d.epilogue, d.wrap_pad, d.crop, d.dtype, d.out_dtype, _, d.res_dtype, d.res_ld, _, d.rowvec_ld, _, d.out_ld,
+     d.a_bstride, d.w_bstride, d.out_bstride, d.res_bstride, d.split3, d.subpixel) = pkey
+    return d
+
+
+def _conv_plan(d, want_moments):
+    """pf_conv_gemm_plan of a descriptor: the library's plan of the launch with / without GroupNorm moments."""
+    g = ConvPlan()
+    check(_lib.lib().pf_conv_gemm_plan(C.byref(d), want_moments, C.byref(g)), "pf_conv_gemm_plan")
+    return g
+
+
 def gemm_workspace_bytes(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, stride=1, pad=0,
                          upsample=0, batch=1, wrap_pad=0, crop=0, subpixel=False, **_):
-    """Split-K scratch pf_conv_gemm wants for this problem (0: the K range is not split)."""
-    d = ConvDesc()
-    d.c0, d.c1 = a0.shape[-1], (a1.shape[-1] if a1 is not None else 0)
-    d.a1 = _p(a1)
+    """Split-K scratch pf_conv_gemm wants for this problem (0: the K range is not split): room for the launch with and the
+    launch without GroupNorm moments."""
+    c0, c1 = a0.shape[-1], (a1.shape[-1] if a1 is not None else 0)
     if w_in is None:
         w_in = a0.numel() // (a0.shape[-1] * max(batch, 1))
-    d.n_img, d.ksize, d.batch, d.n_out = n_img, ksize, batch, n_out
-    d.wrap_pad, d.crop, d.subpixel = wrap_pad, crop, int(bool(subpixel))
-    d.h_out = ((h_in << upsample) + 2 * pad - ksize) // stride + 1
-    d.w_out = (((w_in + 2 * wrap_pad) << upsample) + 2 * pad - ksize) // stride + 1 - 2 * crop
-    return _lib.lib().pf_conv_gemm_workspace_size(C.byref(d))
+    h_out = ((h_in << upsample) + 2 * pad - ksize) // stride + 1
+    w_out = (((w_in + 2 * wrap_pad) << upsample) + 2 * pad - ksize) // stride + 1 - 2 * crop
+    d = _conv_desc((c0, c1, c0, c1, n_img, h_in, w_in, h_out, w_out, ksize, stride, pad, upsample, n_out, batch, 0, wrap_pad, crop,
+                    dt(a0), dt(a0), False, dt(a0), 0, False, 0, False, n_out, 0, 0, 0, 0, False, bool(subpixel)))
+    d.a1 = _p(a1)
+    return max(_conv_plan(d, 0).workspace_bytes, _conv_plan(d, 1).workspace_bytes)
 
 
 # ---- weight-stationary linear (pf_linear_ws): the C = 320 token layers

@@ -1516,3 +1516,85 @@ def test_conv_gemm_subpixel_upsample_in_split_precision(wrap):
     if wrap:
         want = want[..., 2:-2]
     check("split-precision sub-pixel upsampling conv", got, want.permute(0, 2, 3, 1).reshape(-1, cout), 5e-6)
+
+
+# ------------------------------------------------------------------------------------ one plan per problem (pf_conv_gemm_plan)
+
+# (plan class of tests/gemm_plan_grid.py, PF_GEMM32, moments, problem): the smallest problems tools/make_golden_gemm_plans.py prints per class
+PLAN_CLASS_CASES = [
+    ("4wave_mrep2_moments", False, True, dict(n_img=1, h_in=1, w_in=64, c0=64, n_out=128)),
+    ("4wave_deep_ring", False, False, dict(n_img=1, h_in=1, w_in=64, c0=128, n_out=64, a1=True)),
+    ("4wave_deep_ring_split", False, False, dict(n_img=1, h_in=1, w_in=64, c0=128, n_out=64, ksize=3, pad=1)),
+    ("4wave_split", False, False, dict(n_img=8, h_in=32, w_in=64, c0=128, n_out=64, ksize=3, pad=1, wrap_pad=2)),
+    ("8wave_128_moments", False, True, dict(n_img=4, h_in=64, w_in=128, c0=64, n_out=128)),
+    ("8wave_256", False, False, dict(n_img=4, h_in=64, w_in=128, c0=128, n_out=64, ksize=3, pad=1, a1=True)),
+    ("8wave_256_moments", False, True, dict(n_img=1, h_in=64, w_in=128, c0=128, n_out=512, ksize=3, pad=1, a1=True)),
+    ("8wave_split", False, False, dict(n_img=1, h_in=64, w_in=128, c0=2560, n_out=64)),
+    ("8wave_tail_split", False, False, dict(n_img=8, h_in=64, w_in=128, c0=320, n_out=64, ksize=3, pad=1, wrap_pad=2)),
+    ("k32_whole_rounds", True, False, dict(n_img=8, h_in=64, w_in=128, c0=320, n_out=320, ksize=3, pad=1)),
+    ("k32_moments", True, True, dict(n_img=8, h_in=64, w_in=128, c0=320, n_out=320, ksize=3, pad=1)),
+    ("k32_tail", True, False, dict(n_img=2, h_in=1, w_in=40960, c0=320, n_out=320, ksize=3, pad=1)),
+    # moments asked of a problem whose 32x32 plan has a split tail: the 16x16 plan that can emit them serves the launch
+    ("8wave_256_moments", True, True, dict(n_img=2, h_in=1, w_in=40960, c0=320, n_out=320, ksize=3, pad=1)),
+    ("subpixel", False, False, dict(n_img=1, h_in=1, w_in=64, c0=64, n_out=64, ksize=3, pad=1, upsample=1, subpixel=1)),
+    ("subpixel_moments", False, True, dict(n_img=1, h_in=1, w_in=64, c0=64, n_out=128, ksize=3, pad=1, upsample=1, subpixel=1)),
+]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", PLAN_CLASS_CASES, ids=["%s%s" % (c[0], "_g32" if c[1] else "") for c in PLAN_CLASS_CASES])
+def test_conv_gemm_plan_classes(dtype, case, monkeypatch):
+    """Every arm of pf_conv_gemm's dispatch on its plan (pf_conv_gemm_plan), on the smallest problem of the class: the plan reports the
+    intended class first (so a case cannot silently run another arm), then the launch -- scratch of exactly the plan's workspace_bytes,
+    moments where the plan has rows for them -- equals torch's fp32 convolution of the same 16-bit operands to one rounding of the
+    output, and the moments have one part per run of the plan's R rows."""
+    import gemm_plan_grid as GP
+    from panfusion_amd import _lib, engine
+    o = ops()
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    cls, g32, moments, p = case
+    o._PLANS.plans.clear()
+    monkeypatch.setenv("PF_GEMM32", "1" if g32 else "0")
+    plan = GP.plan(_lib.lib(), GP.descriptor(dtype=o.dt(dtype), **p), int(moments))
+    fields = {f: getattr(plan, f) for f in GP.PLAN_FIELDS}
+    assert GP.plan_class(p, fields) == cls, fields
+    assert (plan.gn_rows > 0) == moments
+    n, h, w, cin, cout, ks = p["n_img"], p["h_in"], p["w_in"], p["c0"], p["n_out"], p.get("ksize", 1)
+    ctot = cin * (2 if p.get("a1") else 1)
+    g = torch.Generator(device=DEV).manual_seed(17)
+    x = torch.randn(n, h, w, cin, device=DEV, generator=g).to(dtype)
+    a1 = torch.randn(n, h, w, cin, device=DEV, generator=g).to(dtype) if p.get("a1") else None
+    b = torch.randn(cout, device=DEV, generator=g)
+    kw = dict(n_img=n, h_in=h, w_in=w, ksize=ks, pad=p.get("pad", 0), bias=b, a1=a1, wrap_pad=p.get("wrap_pad", 0))
+    if p.get("subpixel"):
+        conv = torch.nn.Conv2d(cin, cout, 3, padding=1).to(DEV)
+        wq = engine._subpixel_weight(conv, DEV, dtype)
+        kw.update(upsample=1, subpixel=True)
+        xin, w4f = x.float().permute(0, 3, 1, 2), wq.float().reshape(4, cout, 2, 2, cin)      # the four phase convolutions, same rounded weights
+        y = torch.zeros(n, cout, 2 * h, 2 * w, device=DEV)
+        for a in range(2):
+            for c in range(2):
+                y[:, :, a::2, c::2] = F.conv2d(F.pad(xin, (1 - c, c, 1 - a, a)), w4f[2 * a + c].permute(0, 3, 1, 2).contiguous())
+        want = (y + b[None, :, None, None]).permute(0, 2, 3, 1).reshape(-1, cout)
+    else:
+        wq = (torch.randn(cout, ks * ks * ctot, device=DEV, generator=g) / (ks * ks * ctot) ** 0.5).to(dtype)
+        if h == 1 and ks == 3:
+            # one image row: the taps above and below read zero padding, the convolution is the middle kernel row along the width -- as a
+            # product of the three shifted copies (torch's convolution takes over a minute to pick an algorithm for a 1 x 40960 image)
+            xp = F.pad(x.float()[:, 0], (0, 0, 1, 1))                                          # [n, w + 2, c]
+            cols = torch.cat([xp[:, k:k + w] for k in range(3)], -1).reshape(n * w, 3 * cin)
+            want = cols @ wq.float().reshape(cout, 3, 3 * cin)[:, 1].t() + b
+        else:
+            want = _conv_ref_gpu([x] + ([a1] if a1 is not None else []), wq, cout, ks, b, wrap=p.get("wrap_pad", 0))
+    try:
+        got = o.conv_gemm(x, wq, cout, gn_stats=moments, **kw)
+    finally:
+        o._PLANS.plans.clear()
+    check("plan class " + cls, got, want, TOL[dtype])
+    M = want.shape[0]
+    assert got.shape == (M, cout)
+    if moments:
+        assert got._pf_gn[1] == plan.gn_rows and got._pf_gn[0].shape == (M // plan.gn_rows, 2, cout // 2)
+    else:
+        assert not hasattr(got, "_pf_gn")
