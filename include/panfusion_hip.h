@@ -385,6 +385,15 @@ typedef struct {
                           * residual, GEGLU / pair epilogue; split3 allowed: c0 = 2 x channels per tap), batch 1, h_out / w_out even; wrap_pad 0..1 with crop 2 x wrap_pad is the
                           * panorama's pad 1 / upsample / conv / crop 2.  gn_partial is supported (runs of R LOW-resolution rows).            */
     int gn_rows;         /* with gn_partial: the rows per moment run R that gn_partial was sized for (pf_conv_plan.gn_rows); else unused */
+    int a_src_dtype;     /* 0: a0 / a1 hold `dtype` elements (everything above).  PF_F32 (with split3 = 1, ksize = 1, batch = 1): a0 / a1 are the
+                          * fp32 stream tensors THEMSELVES, [rows][a0_ld] / [rows][a1_ld] fp32 with c0 / c1 fp32 channels (multiples of 32; a1
+                          * allowed: x | skip), and the kernels form the pair in registers while they stage a K block -- v = a, or
+                          * v = fma(a, a_scale[img][c], a_shift[img][c]); hi = round16(v), lo = round16(v - hi) -- instead of reading a pair
+                          * tensor that pf_scale_shift_act(out_split) wrote.  Same bytes in, no pair tensor; w, the plan (K = 2 (c0 + c1)) and
+                          * the result are those of the pair form, bit for bit.                                                            */
+    const float* a_scale;/* with a_src_dtype = PF_F32: optional GroupNorm scale [n_img][c0 + c1] fp32 (pf_groupnorm_scale_shift), image of a
+                          * row = row / (h_out * w_out); NULL: the sources are split as they are                                         */
+    const float* a_shift;/* given exactly when a_scale is                                                                                */
 } pf_conv_desc;
 
 enum { PF_EPILOGUE_NONE = 0, PF_EPILOGUE_GEGLU = 1, PF_EPILOGUE_SPLIT = 2 };

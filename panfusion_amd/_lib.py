@@ -33,6 +33,7 @@ class ConvDesc(C.Structure):
         ("epilogue", c_int), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
         ("gn_partial", c_void_p), ("wrap_pad", c_int), ("crop", c_int),
         ("tickets", c_void_p), ("n_tickets", c_int), ("split3", c_int), ("subpixel", c_int), ("gn_rows", c_int),
+        ("a_src_dtype", c_int), ("a_scale", c_void_p), ("a_shift", c_void_p),
     ]
 
 

@@ -80,6 +80,25 @@ template <typename T> __device__ __forceinline__ u16x8 pack8(const float (&f)[8]
 // K block of the GEMM kernels then holds hi and lo of the SAME 32 channels (pf_conv_desc.split3).
 __host__ __device__ __forceinline__ int pair_off(int c) { return ((c >> 5) << 6) | (c & 31); }
 
+// The GroupNorm affine map and the split of an fp32 octet into the pair's two 16-bit octets, hi = round16(v), lo = round16(v - hi).
+// ONE definition for the pass that writes a pair tensor (k_scale_shift_act) and for the tile GEMMs that form the pair while they
+// stage an fp32 source (pf_conv_desc.a_src_dtype): an explicit fma, so that both round alike whatever the compiler would contract.
+// The fma's result is made a COMPLETE fp32 value (the empty asm) before anything rounds it to 16 bit: hipcc otherwise fuses fma + conversion into
+// v_fma_mixlo / mixhi_f16 -- ONE rounding instead of two -- in some kernels (the 8-wave GEMM's staging) and not in others (k_scale_shift_act: v_pk_fma_f32 +
+// v_cvt_pk_f16_f32), and hi then differs in the double-rounding cases (1e-6 of the GEMM's output).
+__device__ __forceinline__ float affine_f(float v, float scale, float shift) {
+    float r = __builtin_fmaf(v, scale, shift);
+    asm("" : "+v"(r));
+    return r;
+}
+template <typename T> __device__ __forceinline__ void split8(const float (&f)[8], u16x8& hi, u16x8& lo) {
+    hi = pack8<T>(f);
+    float r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = f[j] - to_f32<T>(hi[j]);
+    lo = pack8<T>(r);
+}
+
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 
 // Element access by storage tag (fp32 / bf16 / fp16) for the kernels that take any of the three.

@@ -342,12 +342,10 @@ __global__ __launch_bounds__(256) void k_scale_shift_act(const typename In8<TI>:
         if (j0 + u >= per_img) break;
         if (raw_pair) {
             unsigned short* y = raw_pair + pix[u] * (2 * C) + pair_off(cc[u]);
-            const u16x8 hi = pack8<T>(v[u]);
-            float lo[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) lo[j] = v[u][j] - to_f32<T>(hi[j]);
+            u16x8 hi, lo;
+            split8<T>(v[u], hi, lo);
             *reinterpret_cast<u16x8*>(y) = hi;
-            *reinterpret_cast<u16x8*>(y + 32) = pack8<T>(lo);
+            *reinterpret_cast<u16x8*>(y + 32) = lo;
         }
         float f[8];
         if (scale) {
@@ -357,7 +355,7 @@ __global__ __launch_bounds__(256) void k_scale_shift_act(const typename In8<TI>:
             const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
             const float hv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = v[u][j] * sv[j] + hv[j];
+            for (int j = 0; j < 8; ++j) f[j] = affine_f(v[u][j], sv[j], hv[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = v[u][j];
@@ -371,12 +369,10 @@ __global__ __launch_bounds__(256) void k_scale_shift_act(const typename In8<TI>:
             *reinterpret_cast<u16x8*>(static_cast<unsigned short*>(yv) + pix[u] * C + cc[u]) = pack8<T>(f);
         } else if (OUT == 1) {
             unsigned short* y = static_cast<unsigned short*>(yv) + pix[u] * (2 * C) + pair_off(cc[u]);
-            const u16x8 hi = pack8<T>(f);
-            float lo[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) lo[j] = f[j] - to_f32<T>(hi[j]);
+            u16x8 hi, lo;
+            split8<T>(f, hi, lo);
             *reinterpret_cast<u16x8*>(y) = hi;
-            *reinterpret_cast<u16x8*>(y + 32) = pack8<T>(lo);
+            *reinterpret_cast<u16x8*>(y + 32) = lo;
         } else {
             store8_f32(static_cast<float*>(yv) + pix[u] * C + cc[u], f);
         }

@@ -536,9 +536,15 @@ __device__ __forceinline__ void splitk_finish(const GemmParams& p, long bz, int 
 // ran 20 steps in 20.8 us, 0.1 of peak).  4 = one block per CU (115 KB), stage it+3 requested while stage it is multiplied and awaited with a
 // COUNTED s_waitcnt that leaves the two younger stages in flight: the launch-latency-bound problems whose grid is one round of the chip
 // anyway (180 launches per step; the floor of every sharded rank).
-template <typename T, int MREP, int NREP, bool STATS = false, bool S3 = false, int STAGES = 2>
+// A32 (pf_conv_desc.a_src_dtype = PF_F32; S3, two slots, 1x1): the activation operand is the fp32 stream itself.  Thread t owns the octet 8 (t & 3) of the
+// rows (t >> 2) + 64 u of the tile: the 8 fp32 channels of K block it + 1 are requested into registers (buffer loads: rows past M read as zero -- with a_scale they become the image's shift; such rows are never stored and the moment phase masks them) in front of the
+// weight DMA of that block, stay in flight during the MFMAs of block it, and become the two 16-byte pieces hi | lo (affine_f / split8, pf_common.h) that the
+// DMA of the pair tensor would have put at lds_off(row, c4) and lds_off(row, c4 + 4) -- written behind the same full drain and in front of the same barrier
+// that ends the step.  Fragment reads, MFMA order, split-K and every epilogue are the pair form's: the result is bit-identical.
+template <typename T, int MREP, int NREP, bool STATS = false, bool S3 = false, int STAGES = 2, bool A32 = false>
 __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const GemmParams p) {
     constexpr int BM = 32 * MREP, BN = 32 * NREP;
+    static_assert(!A32 || (S3 && STAGES == 2 && MREP % 2 == 0), "fp32-source staging: split-precision walk, two slots");
     extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
     unsigned short* As = smem;                       // [STAGES][BM][64]
     unsigned short* Bs = smem + STAGES * BM * 64;    // [STAGES][BN][64]
@@ -616,6 +622,7 @@ __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const Gem
         const int ky = p.ksize == 3 ? tap / 3 : p.ksize == 2 ? tap >> 1 : 0, kx = p.ksize == 3 ? tap - 3 * ky : p.ksize == 2 ? tap & 1 : 0;
         seg1 = __builtin_amdgcn_readfirstlane(cc >= p.c0 ? 1 : 0) != 0;
         const int ld = seg1 ? p.a1_ld : p.a0_ld;
+        if constexpr (A32) return;                                // (1x1: a row IS its pixel; a32_load addresses it)
         if (p.fastseg) {
             const unsigned sel = (1u << ky) | (16u << kx);
             const int tap_pix = ky * p.w_in + kx;
@@ -642,13 +649,50 @@ __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const Gem
     auto lds_dma = [&](const __amdgpu_buffer_rsrc_t& r, unsigned short* dst, unsigned voff, int soff) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
     };
+    // fp32-source staging (A32): registers of the K block in flight
+    constexpr int NP32 = A32 ? MREP / 2 : 1;                      // octets per thread: BM rows x 4 octets over 256 threads
+    const int c4 = t & 3, r32 = t >> 2;
+    f32x4 xr[NP32][2], sr[NP32][2], hr[NP32][2];
+    auto a32_load = [&](const __amdgpu_buffer_rsrc_t& rs_a, int soff_a) {
+        const int ld = seg1 ? p.a1_ld : p.a0_ld;
+#pragma unroll
+        for (int u = 0; u < NP32; ++u) {
+            const int m = m0 + 64 * u + r32;
+            const unsigned voff = m < p.M ? (static_cast<unsigned>(m) * static_cast<unsigned>(ld) + 8u * c4) * 4u : OOB;
+            xr[u][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, voff, soff_a, 0));
+            xr[u][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, voff + 16u, soff_a, 0));
+            if (p.a_scale) {
+                const long so = static_cast<long>(min(m, p.M - 1) / p.rows_per_img) * (Ctot >> 1) + (cc >> 1) + 8 * c4;
+                sr[u][0] = *reinterpret_cast<const f32x4*>(p.a_scale + so); sr[u][1] = *reinterpret_cast<const f32x4*>(p.a_scale + so + 4);
+                hr[u][0] = *reinterpret_cast<const f32x4*>(p.a_shift + so); hr[u][1] = *reinterpret_cast<const f32x4*>(p.a_shift + so + 4);
+            }
+        }
+    };
+    auto a32_write = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < NP32; ++u) {
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = xr[u][j >> 2][j & 3];
+            if (p.a_scale) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = affine_f(f[j], sr[u][j >> 2][j & 3], hr[u][j >> 2][j & 3]);
+            }
+            u16x8 hi, lo;
+            split8<T>(f, hi, lo);
+            unsigned short* dst = As + buf * BM * 64;
+            *reinterpret_cast<u16x8*>(dst + lds_off(64 * u + r32, c4)) = hi;
+            *reinterpret_cast<u16x8*>(dst + lds_off(64 * u + r32, c4 + 4)) = lo;
+        }
+    };
     auto dma_stage = [&](int buf) {
-        const int soff_a = __builtin_amdgcn_readfirstlane((seg1 ? cc - p.c0 : cc) * 2);
+        const int soff_a = __builtin_amdgcn_readfirstlane((seg1 ? cc - p.c0 : cc) * 2);      // (A32: pair offset / 2 channels x 4 bytes -- the same number)
         const int soff_w = __builtin_amdgcn_readfirstlane(kg * 2);
         const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
             uniform_ptr(seg1 ? a1 : a0), 0, __builtin_amdgcn_readfirstlane(seg1 ? p.a1_bytes : p.a0_bytes), 0x00020000);
+        if constexpr (A32) a32_load(rs_a, soff_a);
 #pragma unroll
-        for (int i = 0; i < MREP; ++i) {
+        for (int i = 0; i < (A32 ? 0 : MREP); ++i) {
             unsigned short* dst = As + buf * BM * 64 + (i * 32 + wave * 8) * 64;
             lds_dma(rs_a, dst, a_off[i], soff_a);
         }
@@ -720,12 +764,15 @@ __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const Gem
     if constexpr (STAGES == 2) {
         dma_stage(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (A32) a32_write(0);
         __syncthreads();
         stamp(p, 1);
         for (int kb = kb0, it = 0; kb < kb1; ++kb, ++it) {
             if (kb + 1 < kb1) dma_stage((it + 1) & 1);            // in flight during the MFMAs
             compute(it & 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave's DMA has landed ...
+            if constexpr (A32) { if (kb + 1 < kb1) a32_write((it + 1) & 1); }   // (its fp32 octets too: the slot was retired by the previous barrier;
+                                                                  // __syncthreads waits for the ds_writes -- lgkmcnt(0) -- in front of its barrier)
             __syncthreads();                                      // ... before anyone reads the tile
         }
     } else {
@@ -786,7 +833,21 @@ __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const Gem
 // by the lower 32 lanes of all 8 waves), so one immediate serves all.
 // Tile boundary: right after the barrier that retires the ring the block decodes its next tile and requests
 // that tile's first two stages into slots 0 / 1; the epilogue runs meanwhile in two row slices through slot 2.
-template <typename T, int NREP, int NW, bool STATS = false, bool S3 = false, int BM_ = 256>
+// A32 (pf_conv_desc.a_src_dtype = PF_F32; split-precision 1x1 walk): the activation operand is the fp32 stream itself.  Thread t owns the octet 8 (t & 3) of
+// tile rows 2 (t >> 2) + u, u < 2: the four 16-byte buffer loads of its two octets take the places (and the issue slots between the MFMAs of the
+// second half) of the four activation DMA pieces of the stage requested there, stay in registers for half a K step, and are turned into the pieces
+// hi | lo at lds_off(row, c4) / lds_off(row, c4 + 4) (affine_f / split8, pf_common.h) behind the first MFMA group of the NEXT step -- in front of the
+// mid-step barrier that the stage's first fragment reads wait behind (two slots), or one step ahead of it (three).  Counted waits: the octets are
+// consumed (the compiler's own vmcnt in front of the conversion) before every explicit wait, so what may stay in flight there is the weight pieces of the
+// youngest stage alone: NPIECE - APASS instead of NPIECE; the ds_writes are covered by the lgkmcnt(0) of the mid-step wait.
+// AFF (a_scale / a_shift given): the scale / shift octet of a stage is requested behind the (W_lo, A_hi) group of the step that requests the stage -- the
+// W_lo fragments are dead from there on -- and the conversion runs in front of the next step's fragment requests, while the second fragment set is dead:
+// with the affine registers live next to all four fragment sets the 160-column kernels spilled (108-364 bytes of scratch per lane).
+// Cost, stated and not measured in isolation: the four scale / shift loads are YOUNGER than the stage's weight pieces, so the compiler's wait in front of the
+// next step's conversion is vmcnt(0) and the youngest weight stage has landed half a step after its request -- on the three-slot 256 x 128 tile that gives up
+// the second step of look-ahead the explicit vmcnt(NPIECE - APASS) would leave it (the two-slot blocks drain fully at that point anyway).  Requested in
+// front of the weight pieces the octet is live across the (W_lo, A_hi) group and the 160-column kernels spill again.
+template <typename T, int NREP, int NW, bool STATS = false, bool S3 = false, int BM_ = 256, bool A32 = false, bool AFF = false>
 __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(const GemmParams p) {
     // NW = 8: 4 x 2 waves, 64x80 per wave, two waves per SIMD.  NW = 4, BM_ = 256: 2 x 2 waves, 128x80 per wave, ONE wave
     // per SIMD with the whole register file (160 accumulator + 104 fragment registers): twice the MFMAs per
@@ -821,6 +882,13 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     const int hchunk8 = (chunk ^ ((hrow >> 1) & 7)) * 8;
 
     constexpr int APASS = BM / RPP;                  // DMA passes of the activation tile
+    static_assert(!A32 || (S3 && APASS == 4 && BM * 4 == NT * 2), "fp32-source staging: two octets = four 16-byte loads per thread and stage");
+    struct XR { f32x4 x[2][2], s[2], h[2]; int cc; };   // A32: a stage's two fp32 octets (+ the scale / shift of their 8 channels, cc = its pair channel) in flight
+    XR xq;
+    const int c4 = t & 3, r32 = 2 * (t >> 2);        // A32: octet and first of the two (adjacent) tile rows of this thread -- rows 2 q, 2 q + 1 belong to ONE
+                                                     // image (rows per image are even: pf_conv_gemm checks), so one scale / shift octet serves both
+    unsigned x_off[2];                               // bytes, or OOB
+    int x_sidx = 0;                                  // element of a_scale / a_shift at channel 0 of the octet
     int a_img[APASS], a_y[APASS], a_x[APASS];
     // DMA addressing: buffer descriptors (SGPR) + a per-thread 32-bit byte offset (VGPR) + a per-stage
     // scalar byte offset (soffset), so that a piece costs no vector ALU work per K step -- the kernel is
@@ -862,6 +930,14 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
         const int ky = p.ksize == 3 ? tap / 3 : p.ksize == 2 ? tap >> 1 : 0, kx = p.ksize == 3 ? tap - 3 * ky : p.ksize == 2 ? tap & 1 : 0;
         seg1 = __builtin_amdgcn_readfirstlane(cc >= p.c0 ? 1 : 0) != 0;
         const int ld = seg1 ? p.a1_ld : p.a0_ld;
+        if constexpr (A32) {                                           // 1x1: a row IS its pixel; rows past M read as zero (and become `shift` under the affine map: never stored, masked in the moments)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int m = m0 + r32 + u;
+                x_off[u] = m < p.M ? (static_cast<unsigned>(m) * static_cast<unsigned>(ld) + 8u * c4) * 4u : OOB;
+            }
+            return;
+        }
         if (p.fastseg) {                                               // (pf_gemm_params.h: a_img = pixel index, a_y = validity bits)
             const unsigned sel = (1u << ky) | (16u << kx);
             const int tap_pix = ky * p.w_in + kx;
@@ -929,6 +1005,9 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
         kg = kb0 * 64;
         tap = kg / Ctot;
         cc = kg - tap * Ctot;
+        if constexpr (A32) {
+            if constexpr (AFF) x_sidx = (min(m0 + r32, p.M - 1) / p.rows_per_img) * (Ctot >> 1) + 8 * c4;
+        }
         set_segment();
 #ifdef PF_GEMM_BDIRECT
         kw = kb0 * 64;
@@ -960,10 +1039,16 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     auto lds_dma = [&](const __amdgpu_buffer_rsrc_t& r, unsigned short* dst, unsigned voff, int soff) __attribute__((always_inline)) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
     };
-    auto dma_piece = [&](const __amdgpu_buffer_rsrc_t& rs_a, int slot, int k) __attribute__((always_inline)) {
+    auto dma_piece = [&](const __amdgpu_buffer_rsrc_t& rs_a, int slot, int k, XR& q) __attribute__((always_inline)) {
         unsigned short* As = smem + slot * STAGE;
         unsigned short* Bs = As + BM * 64;
         if (k < APASS) {
+            if constexpr (A32) {                                  // half an fp32 octet into registers (a32_write puts it into the slot)
+                const int u = k >> 1, hf = k & 1;
+                q.x[u][hf] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, x_off[u] + 16u * hf, st_soff_a, 0));
+                if (k == 0) q.cc = cc;
+                return;
+            }
             unsigned short* dst = As + (k * RPP + wave * 8) * 64;
             lds_dma(rs_a, dst, a_off[k], st_soff_a);
 #ifdef PF_GEMM_BDIRECT
@@ -976,11 +1061,41 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
             if (lane < 32) lds_dma(rs_w, Bs + (BFULL * RPP + wave * 4) * 64, w_off[BFULL], st_soff_w);
         }
     };
-    auto dma_stage = [&](int slot) __attribute__((always_inline)) {
+    auto dma_stage = [&](int slot, XR& q) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rs_a = stage_begin();
 #pragma unroll
-        for (int k = 0; k < NPIECE; ++k) dma_piece(rs_a, slot, k);
+        for (int k = 0; k < NPIECE; ++k) dma_piece(rs_a, slot, k, q);
         stage_end();
+    };
+    // A32 + AFF: scale / shift of the 8 channels of the stage in q
+    auto a32_affine = [&](XR& q) __attribute__((always_inline)) {
+        if constexpr (A32 && AFF) {
+            const int so = x_sidx + (q.cc >> 1);
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                q.s[hf] = *reinterpret_cast<const f32x4*>(p.a_scale + so + 4 * hf);
+                q.h[hf] = *reinterpret_cast<const f32x4*>(p.a_shift + so + 4 * hf);
+            }
+        }
+    };
+    // A32: registers of a stage -> its activation image in ring slot `slot`
+    auto a32_write = [&](int slot, const XR& q) __attribute__((always_inline)) {
+        unsigned short* As = smem + slot * STAGE;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = q.x[u][j >> 2][j & 3];
+            if constexpr (AFF) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = affine_f(f[j], q.s[j >> 2][j & 3], q.h[j >> 2][j & 3]);
+            }
+            u16x8 hi, lo;
+            split8<T>(f, hi, lo);
+            const int row = r32 + u;
+            *reinterpret_cast<u16x8*>(As + lds_off(row, c4)) = hi;
+            *reinterpret_cast<u16x8*>(As + lds_off(row, c4 + 4)) = lo;
+        }
     };
 
     f32x4 acc[MREP][NREP];
@@ -1042,8 +1157,22 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     };
 
     auto issue_prologue = [&]() __attribute__((always_inline)) {
-        dma_stage(0);
-        if (n_it > 1) dma_stage(1);
+        if constexpr (A32 && STAGES == 3) {                // both stages requested, then both written (the fragment registers are dead here)
+            XR q0;
+            dma_stage(0, q0);
+            a32_affine(q0);
+            if (n_it > 1) { dma_stage(1, xq); a32_affine(xq); }
+            a32_write(0, q0);
+            if (n_it > 1) a32_write(1, xq);
+        } else if constexpr (A32) {                               // two slots: stage 1 stays in registers, step 0 writes it in front of its barrier
+            dma_stage(0, xq);
+            a32_affine(xq);
+            a32_write(0, xq);
+            if (n_it > 1) { dma_stage(1, xq); a32_affine(xq); }
+        } else {
+            dma_stage(0, xq);
+            if (n_it > 1) dma_stage(1, xq);
+        }
     };
     const std::true_type YES;
     const std::false_type NO;
@@ -1076,6 +1205,16 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
 #else
             if (idx == FLEAD - 1) {
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (A32) {
+                    // the octets requested during the previous step (or by the prologue) become stage it + STAGES - 1 in LDS, while the second fragment set is
+                    // still dead: three slots -- the steps that still await a younger stage (WAIT != 0) -- into the slot retired one step ago; two slots --
+                    // every step that has a successor -- into the other slot
+                    constexpr bool PEND = STAGES == 3 ? WAIT != 0 : MORE;
+                    if constexpr (PEND) {
+                        a32_write(STAGES == 3 ? nx2 : nx1, xq);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
 #ifndef PF_ABL_NOLDS
                 load_frags(cur, 1, fa1, fb1, 0);
 #endif
@@ -1089,6 +1228,8 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
         if constexpr (MORE) {
             // my pieces of the next stage have landed (the stage after it may still be in flight: WAIT), and my
             // reads of the current slot have returned -- it is refilled right after the barrier
+            if constexpr (A32 && WAIT != 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(WAIT) : "memory");
+            else
 #ifdef PF_GEMM_BDIRECT
             if constexpr (true) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #else
@@ -1121,11 +1262,12 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
                     const int k = idx - LEAD;
                     if (k >= 0 && (k & 1) == 0 && (k >> 1) < NPIECE) {
                         __builtin_amdgcn_sched_barrier(0);
-                        dma_piece(rs_a, cur, k >> 1);
+                        dma_piece(rs_a, cur, k >> 1, xq);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             }
+            if constexpr (DMA) { __builtin_amdgcn_sched_barrier(0); a32_affine(xq); }
             if (MORE) { __builtin_amdgcn_sched_barrier(0); load_frags_a(nx1, 0, fa0); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
             for (int j = 0; j < NREP; ++j) {
@@ -1163,7 +1305,7 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
 #ifdef PF_ABL_NODMA_B         /* timing-only: activation pieces only */
                     if ((k >> 1) < APASS)
 #endif
-                    dma_piece(rs_a, cur, k >> 1);                 // stage it+3 into the slot retired at this step's barrier
+                    dma_piece(rs_a, cur, k >> 1, xq);             // stage it+3 into the slot retired at this step's barrier
 #endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1206,6 +1348,8 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
 #pragma unroll
             for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (first && n_it > 1) {                          // stage 0 landed, stage 1 may still fly
+            if constexpr (A32) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPIECE - APASS) : "memory");   // (its weight pieces: the octets of both stages were consumed or are older)
+            else
 #ifdef PF_GEMM_BDIRECT
             if constexpr (true) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
@@ -1220,19 +1364,20 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
         } else {                                          // later tiles: the epilogue's stores sit behind the DMAs in vmcnt
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
+        if constexpr (A32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the prologue's ds_writes
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (first) stamp(p, 1);
         first = false;
         PF_TL(p, tl_tile == 1, 13);
-        if constexpr (STAGES == 3) { if (n_it > 2) dma_stage(2); }   // third stage in flight (slot 2 staged the previous tile's epilogue)
+        if constexpr (STAGES == 3) { if (n_it > 2) { dma_stage(2, xq); a32_affine(xq); } }   // third stage in flight (slot 2 staged the previous tile's epilogue)
         load_frags(0, 0, fa0, fb0, 0);
         cur = 0; nx1 = 1; nx2 = 2 % STAGES;
         PF_TL(p, tl_tile == 1, 14);
         // The slot of stage `it` is retired at the mid-step barrier of step `it` (its last fragments are
         // requested in the first half), and stage it+3 is requested into it right behind that barrier: with
         // three slots a stage has TWO K steps to arrive, the mid-step wait leaves the younger one in flight.
-        const std::integral_constant<int, NPIECE> W1;
+        const std::integral_constant<int, A32 ? NPIECE - APASS : NPIECE> W1;
         const std::integral_constant<int, 0> W0;
         if constexpr (STAGES == 3) {
             for (int it = 0; it + 3 < n_it; ++it) step(YES, YES, W1);
@@ -1347,14 +1492,14 @@ pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsign
 
 // The launchers below run ONE pass of a plan's kernel: output rows [p.m_begin, p.M) in p.splits K slices (launch_pass combines the slices).
 
-template <typename T, int MREP, int NREP, bool STATS, bool S3, int STAGES>
+template <typename T, int MREP, int NREP, bool STATS, bool S3, int STAGES, bool A32 = false>
 static pf_status launch_ring(const GemmParams& p, int batch, hipStream_t st) {
     constexpr int BM = 32 * MREP, BN = 32 * NREP;
     const size_t smem = static_cast<size_t>(STAGES) * (BM + BN) * 64 * sizeof(unsigned short);
     static std::atomic<unsigned long long> lds_set{0};
-    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES>), smem, lds_set, "pf_conv_gemm");
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES, A32>), smem, lds_set, "pf_conv_gemm");
     if (s != PF_OK) return s;
-    hipLaunchKernelGGL((k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES>), dim3(p.mtiles * p.ntiles, p.splits, batch), dim3(256), smem, st, p);
+    hipLaunchKernelGGL((k_conv_gemm<T, MREP, NREP, STATS, S3, STAGES, A32>), dim3(p.mtiles * p.ntiles, p.splits, batch), dim3(256), smem, st, p);
     PF_CHECK_LAUNCH("pf_conv_gemm");
     return PF_OK;
 }
@@ -1371,6 +1516,9 @@ static pf_status launch_s(const pf_conv_plan& g, const GemmParams& gp, int batch
     if constexpr (!STATS && !S3) {
         if (g.ring_slots == 4) return launch_ring<T, MREP, NREP, false, false, 4>(p, batch, st);
     }
+    if constexpr (S3) {
+        if (p.a32) return launch_ring<T, MREP, NREP, STATS, true, 2, true>(p, batch, st);      // the fp32-source form of the same kernel arm
+    }
     return launch_ring<T, MREP, NREP, STATS, S3, 2>(p, batch, st);
 }
 
@@ -1380,7 +1528,7 @@ static pf_status launch(const pf_conv_plan& g, const GemmParams& gp, int batch, 
     return gp.gn_partial ? launch_s<T, MREP, NREP, true>(g, gp, batch, st) : launch_s<T, MREP, NREP, false>(g, gp, batch, st);
 }
 
-template <typename T, int NREP, int NW, bool STATS = false, bool S3 = false, int BM = 256>
+template <typename T, int NREP, int NW, bool STATS = false, bool S3 = false, int BM = 256, bool A32 = false, bool AFF = false>
 static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
     constexpr int BN = 32 * NREP, STAGES = BM == 128 ? 2 : 3;
     GemmParams p = gp;
@@ -1396,7 +1544,7 @@ static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
     p.prof = (ps.buf && static_cast<long>(p.mtiles) * p.ntiles * p.splits * batch <= ps.blocks) ? ps.buf : nullptr;
     const size_t smem = static_cast<size_t>(STAGES) * (BM + BN) * 64 * sizeof(unsigned short);
     static std::atomic<unsigned long long> lds_set{0};
-    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm8<T, NREP, NW, STATS, S3, BM>), smem, lds_set, "pf_conv_gemm (8-wave)");
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_conv_gemm8<T, NREP, NW, STATS, S3, BM, A32, AFF>), smem, lds_set, "pf_conv_gemm (8-wave)");
     if (s != PF_OK) return s;
     // persistent over tiles: one block per CU walks tiles b, b + grid, ... (a multiple of 8 keeps a tile on
     // the XCD its id maps to); PF_GEMM8_PERSIST=0 launches one block per tile
@@ -1408,7 +1556,7 @@ static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
         if (gx >= 8) gx = gx / 8 * 8;
         grid = std::min(grid, gx);
     }
-    hipLaunchKernelGGL((k_conv_gemm8<T, NREP, NW, STATS, S3, BM>), dim3(grid, p.splits, batch), dim3(64 * NW), smem, st, p);
+    hipLaunchKernelGGL((k_conv_gemm8<T, NREP, NW, STATS, S3, BM, A32, AFF>), dim3(grid, p.splits, batch), dim3(64 * NW), smem, st, p);
     PF_CHECK_LAUNCH("pf_conv_gemm (8-wave)");
     return PF_OK;
 }
@@ -1416,6 +1564,13 @@ static pf_status launch8w_s(const GemmParams& gp, int batch, hipStream_t st) {
 template <typename T, int NREP, int NW, int BM = 256>
 static pf_status launch8w(const GemmParams& gp, int batch, hipStream_t st) {
     if constexpr (NW == 8 || BM == 128) {
+        // fp32 sources (pf_conv_gemm has refused what is not instantiated: moments -- the plan gives this kernel none in that mode -- and the affine map on
+        // the 256 x 160 tile, whose registers do not hold the scale / shift octet without scratch)
+        if (gp.s3 && gp.a32 && gp.a_scale) {
+            if constexpr (NREP == 5 && BM == 256) { set_error("pf_conv_gemm: a_scale on the 256 x 160 tile"); return PF_ERR_ARG; }
+            else return launch8w_s<T, NREP, NW, false, true, BM, true, true>(gp, batch, st);
+        }
+        if (gp.s3 && gp.a32) return launch8w_s<T, NREP, NW, false, true, BM, true>(gp, batch, st);
         if (gp.s3) return gp.gn_partial ? launch8w_s<T, NREP, NW, true, true, BM>(gp, batch, st) : launch8w_s<T, NREP, NW, false, true, BM>(gp, batch, st);
         if (gp.gn_partial) return launch8w_s<T, NREP, NW, true, false, BM>(gp, batch, st);
     }
@@ -1461,6 +1616,18 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     PF_REQUIRE(d->out_dtype == d->dtype || d->out_dtype == PF_F32, "pf_conv_gemm: out_dtype must equal dtype or be PF_F32");
     PF_REQUIRE(!d->residual || d->res_dtype == d->dtype || d->res_dtype == PF_F32, "pf_conv_gemm: res_dtype must equal dtype or be PF_F32");
     const int c1 = d->a1 ? d->c1 : 0;
+    const bool a32 = d->a_src_dtype == PF_F32;                    // fp32 sources, split while they are staged
+    PF_REQUIRE(d->a_src_dtype == 0 || a32, "pf_conv_gemm: a_src_dtype must be 0 (a0 / a1 hold dtype elements) or PF_F32");
+    PF_REQUIRE(a32 || (!d->a_scale && !d->a_shift), "pf_conv_gemm: a_scale / a_shift belong to fp32 sources (a_src_dtype = PF_F32)");
+    if (a32) {
+        PF_REQUIRE(d->split3 && d->ksize == 1 && d->stride == 1 && d->pad == 0 && d->upsample == 0 && d->wrap_pad == 0 && d->crop == 0 && !d->subpixel &&
+                   d->batch == 1, "pf_conv_gemm: fp32 sources serve the split-precision 1x1 walk only (split3, ksize 1, stride 1, no padding, batch 1)");
+        PF_REQUIRE(d->c0 > 0 && d->c0 % 32 == 0 && c1 % 32 == 0, "pf_conv_gemm: fp32 channel counts (%d,%d) must be multiples of 32", d->c0, c1);
+        PF_REQUIRE(d->a0_ld >= d->c0 && d->a0_ld % 4 == 0 && (!d->a1 || (d->a1_ld >= c1 && d->a1_ld % 4 == 0)),
+                   "pf_conv_gemm: leading dimensions of fp32 sources must be >= their channels and multiples of 4");
+        PF_REQUIRE((d->a_scale != nullptr) == (d->a_shift != nullptr), "pf_conv_gemm: a_scale and a_shift come together");
+        PF_REQUIRE((!d->a_scale || aligned16(d->a_scale)) && (!d->a_shift || aligned16(d->a_shift)), "pf_conv_gemm: a_scale / a_shift must be 16-byte aligned");
+    } else
     PF_REQUIRE(d->c0 > 0 && d->c0 % 64 == 0 && c1 % 64 == 0, "pf_conv_gemm: channel counts (%d,%d) must be multiples of 64", d->c0, c1);
     PF_REQUIRE(d->ksize == 1 || d->ksize == 3, "pf_conv_gemm: ksize must be 1 or 3");
     PF_REQUIRE(d->stride == 1 || d->stride == 2, "pf_conv_gemm: stride must be 1 or 2");
@@ -1471,8 +1638,8 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     // out_ld leaves room for the 4-wide store; the extra columns are written as zeros.
     PF_REQUIRE(d->n_out > 0 && (d->n_out % 4 == 0 || (!d->bias && !d->rowvec && !d->residual && d->out_ld >= (d->n_out + 3) / 4 * 4)),
                "pf_conv_gemm: n_out=%d must be a multiple of 4 (or no epilogue operands and a padded out_ld)", d->n_out);
-    PF_REQUIRE(d->a0_ld >= d->c0 && d->a0_ld % 8 == 0, "pf_conv_gemm: a0_ld must be >= c0 and a multiple of 8");
-    PF_REQUIRE(!d->a1 || (d->a1_ld >= c1 && d->a1_ld % 8 == 0), "pf_conv_gemm: a1_ld must be >= c1 and a multiple of 8");
+    PF_REQUIRE(a32 || (d->a0_ld >= d->c0 && d->a0_ld % 8 == 0), "pf_conv_gemm: a0_ld must be >= c0 and a multiple of 8");
+    PF_REQUIRE(a32 || !d->a1 || (d->a1_ld >= c1 && d->a1_ld % 8 == 0), "pf_conv_gemm: a1_ld must be >= c1 and a multiple of 8");
     PF_REQUIRE(d->epilogue == PF_EPILOGUE_GEGLU || (d->out_ld >= d->n_out && d->out_ld % 4 == 0), "pf_conv_gemm: out_ld must be >= n_out and a multiple of 4");
     PF_REQUIRE(!d->residual || (d->res_ld >= d->n_out && d->res_ld % 4 == 0), "pf_conv_gemm: res_ld must be >= n_out and a multiple of 4");
     PF_REQUIRE(!d->rowvec || (d->rowvec_ld >= d->n_out && d->rowvec_ld % 4 == 0), "pf_conv_gemm: rowvec_ld must be >= n_out and a multiple of 4");
@@ -1485,7 +1652,7 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     if (d->epilogue == PF_EPILOGUE_SPLIT)
         PF_REQUIRE(d->n_out % 32 == 0 && d->out_dtype == d->dtype && d->out_ld >= 2 * d->n_out && !d->rowvec,
                    "pf_conv_gemm: SPLIT epilogue needs n_out %% 32 == 0 (hi / lo interleave per 32 columns), a 16-bit output with out_ld >= 2 n_out, no row vector");
-    if (d->split3)
+    if (d->split3 && !a32)
         PF_REQUIRE(!d->a1 && d->c0 % 64 == 0, "pf_conv_gemm: a split-precision walk (split3) takes ONE source of 2 x channels = c0 (hi / lo interleaved per 32)");
     if (d->epilogue == PF_EPILOGUE_GEGLU)
         PF_REQUIRE(d->n_out % 4 == 0 && d->out_dtype == d->dtype && !d->residual && d->out_ld >= d->n_out / 2 && d->out_ld % 2 == 0,
@@ -1510,6 +1677,11 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     GemmParams p;
     params_from_desc(d, p);
     const pf_conv_plan g = plan_conv_gemm(p, batch, d->workspace != nullptr, d->gn_partial != nullptr);
+    // fp32 sources + affine map: every arm but the 256 x 160 tile of the 8-wave kernel (no registers left for the scale / shift octet: 144 bytes of
+    // scratch per lane); the caller runs that problem in the two-launch form (ops.conv_gemm_a32_serves asks the same question of the plan)
+    PF_REQUIRE(!(a32 && d->a_scale && g.kernel == 1 && g.block_rows == 256 && g.nrep == 5),
+               "pf_conv_gemm: a_scale / a_shift are not available on the 256 x 160 tile of the 8-wave kernel (this problem's plan): use the pair form");
+    PF_REQUIRE(!(a32 && d->a_scale) || (d->h_out * d->w_out) % 2 == 0, "pf_conv_gemm: a_scale needs an even number of rows per image");
     if (d->gn_partial) {
         PF_REQUIRE(g.gn_rows > 0, "pf_conv_gemm: gn_partial given but this problem cannot emit GroupNorm moments (ask pf_conv_gemm_gn_rows first)");
         PF_REQUIRE(aligned16(d->gn_partial), "pf_conv_gemm: gn_partial must be 16-byte aligned");
@@ -1521,7 +1693,9 @@ extern "C" pf_status pf_conv_gemm(const pf_conv_desc* d, void* stream) {
     }
     {   // extents for the buffer descriptors of the 8-wave and 32x32 kernels (32-bit offsets, < 2 GiB)
         const long npix = static_cast<long>(d->n_img) * d->h_in * d->w_in;
-        const long a0b = ((npix - 1) * p.a0_ld + p.c0) * 2, a1b = p.a1 ? ((npix - 1) * p.a1_ld + p.c1) * 2 : 0;
+        // (fp32 sources: p.c0 / p.c1 count pair elements = 2 x fp32 channels, of 4 bytes each)
+        const long a0b = a32 ? ((npix - 1) * p.a0_ld + p.c0 / 2) * 4 : ((npix - 1) * p.a0_ld + p.c0) * 2;
+        const long a1b = !p.a1 ? 0 : a32 ? ((npix - 1) * p.a1_ld + p.c1 / 2) * 4 : ((npix - 1) * p.a1_ld + p.c1) * 2;
         const long wb = static_cast<long>(p.N) * p.K * 2;      // (per batch element / sub-pixel phase: the kernels offset the base by w_bs)
         PF_REQUIRE(a0b < (1L << 31) && a1b < (1L << 31) && wb < (1L << 31),
                    "pf_conv_gemm: each operand must be smaller than 2 GiB (32-bit buffer offsets)");

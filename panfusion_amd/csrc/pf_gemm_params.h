@@ -42,6 +42,10 @@ struct GemmParams {
                                    // one validity bit per tap row / tap column (seg_pack) instead of (image, y, x), and the per-tap source offsets are an add, a
                                    // multiply-add and a select (set_segment used to be ~20 dependent vector instructions in front of the next stage's DMA: 5-7 % of a
                                    // 3x3 convolution, profiles/r6_seg_ablate.txt).  PF_CONV_FASTSEG=0: the general form everywhere (A/B)
+    int a32;                       // fp32-source mode of the split-precision 1x1 walk (pf_conv_desc.a_src_dtype = PF_F32): a0 / a1 point at fp32 [rows][a0_ld / a1_ld]
+                                   // (leading dimensions in fp32 elements), c0 / c1 / K stay in PAIR elements (2 x fp32 channels: the K walk, the weights and the plan are those
+                                   // of the pair form) and the kernels build the [hi(32) | lo(32)] image of a K block in LDS from registers instead of by DMA
+    const float* a_scale; const float* a_shift;   // a32: optional per-(image, fp32 channel) affine map applied before the split, [n_img][(c0 + c1) / 2]
     int subpix;                    // nearest x2 upsampling + 3x3 convolution as FOUR 2x2 convolutions on the low-resolution grid (pf_conv_desc.subpixel):
                                    // blockIdx.z = output phase (a, b) = (z >> 1, z & 1); taps of phase a read input rows y - 1 + a, y + a (columns alike): pad = 1 - phase;
                                    // weights [4][N][2][2][C] (w_bs = N K), a_bs = out_bs = 0; M / h_out / w_out / rows_per_img are those of the LOW-resolution grid and

@@ -36,6 +36,9 @@ void params_from_desc(const pf_conv_desc* d, GemmParams& p) {
     p.gn_partial = nullptr; p.gn_rows = 0;
     p.m_begin = 0; p.splits = 1; p.kb_per_split = 0; p.partial = nullptr; p.tickets = nullptr;
     p.a0_bytes = p.a1_bytes = p.w_bytes = 0; p.adv_img = p.adv_y = p.adv_x = 0;
+    p.a32 = d->a_src_dtype == PF_F32;
+    p.a_scale = p.a32 ? d->a_scale : nullptr; p.a_shift = p.a32 ? d->a_shift : nullptr;
+    if (p.a32) { p.c0 = 2 * d->c0; p.c1 = 2 * c1; p.K = 2 * Ctot; }     // pair elements: the problem the planner sees IS the pair form's
     p.subpix = 0;
     p.fastseg = (d->upsample == 0 || d->subpixel) && d->wrap_pad == 0 && GemmTuning::conv_fastseg() ? 1 : 0;
     if (d->subpixel) {
@@ -246,6 +249,7 @@ pf_conv_plan plan_conv_gemm(const GemmParams& p, int batch, bool allow_split, bo
     } else {
         g = plan_tiles(p.M, p.N, p.K, batch, allow_split, p.s3 != 0);
         g.gn_rows = want_moments ? gn_rows16(p, g, batch) : 0;
+        if (p.a32 && g.kernel == 1) g.gn_rows = 0;                  // (fp32 sources: the 8-wave kernel has no moment variant -- its staging registers are what that variant spends)
         if (g.kernel == 1) {
             // 128-row blocks: four waves and a two-slot ring, two blocks per CU.  PF_GEMM8_WAVES=4: one 128x80 wave per SIMD (accumulators in AGPRs)
             // is implemented and correct but measured slower (K step 2520 vs 2222 clocks, epilogue 2x): a lone in-order wave exposes every

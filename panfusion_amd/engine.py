@@ -37,6 +37,8 @@ def default_precision(dtype):
 
 
 RAW_PAIR_FUSED = os.environ.get("PF_RAW_PAIR", "1") != "0"      # A/B: 0 = the shortcut operand by its own split pass
+A32 = os.environ.get("PF_A32", "1") != "0"                      # A/B: 0 = the split-precision 1x1 GEMMs read a pair tensor written by a pass of its own (two launches)
+TAPING = False                                                  # set by train_engine while a forward that the backward will revisit runs
 VIRTUAL_PAD = os.environ.get("PF_VIRTUAL_PAD", "1") != "0"      # A/B: 0 = materialised pad_pano / unpad_pano copies around the panorama convs
 EXACT_UP0 = os.environ.get("PF_EXACT_UP0", "1") != "0"          # A/B: 0 = the level-0 upsampling convolution single-pass 16 bit like the other two (mixed scheme)
 SUBPIXEL_UP = os.environ.get("PF_SUBPIXEL_UP", "1") != "0"      # A/B: 0 = the upsampling convolutions as nearest x2 + 3x3 (9 taps) instead of four 2x2 phase convolutions (4 taps)
@@ -101,6 +103,29 @@ def split_operand(x0, x1=None, scale=None, shift=None, act=0, dtype=None):
     n_img = scale.shape[0] if scale is not None else 1
     hw = x0.numel() // (c * n_img)
     return ops.scale_shift_act(x0, x1, n_img, hw, scale, shift, act, out_dtype=dtype, split=True)
+
+
+def exact_gemm_f32(x0, w3, n_out, dtype, *, x1=None, scale=None, shift=None, save=None, **kw):
+    """exact_gemm(split_operand(x0, x1, scale, shift, 0), ...) in ONE launch where that is possible: the kernel reads the fp32 stream
+    itself and splits it while staging (ops.conv_gemm_a32: bit-identical, no pair tensor through memory).  The two-launch form stays
+    where ops has no such entry, where the call is part of a differentiable forward (save given / the training tape records), under
+    PF_A32=0 (A/B), and for sources the entry does not take."""
+    direct = getattr(ops, "conv_gemm_a32", None)
+    if direct is not None and A32 and save is None and not TAPING and ops.a32_ok(x0, x1):
+        n_img = scale.shape[0] if scale is not None else 1
+        rows = x0.numel() // x0.shape[-1]
+        w_in = kw.pop("w_in", rows)
+        a32 = dict(x1=x1, scale=scale, shift=shift, n_img=n_img, w_in=rows // n_img, **kw)
+        if ops.conv_gemm_a32_serves(x0, w3, n_out, dtype, **a32):
+            return direct(x0, w3, n_out, dtype, **a32)
+        kw["w_in"] = w_in
+    return exact_gemm(split_operand(x0, x1, scale, shift, 0, dtype=dtype), w3, n_out, **kw)
+
+
+def _a32_shortcut(r, x, skip, save):
+    """Does the resnet's split-precision shortcut read x | skip itself (exact_gemm_f32's one-launch form)?"""
+    return (r.ws3 is not None and A32 and save is None and not TAPING and getattr(ops, "conv_gemm_a32", None) is not None
+            and ops.a32_ok(x, skip))
 
 
 def exact_gemm(a_split, w3, n_out, **kw):
@@ -461,7 +486,8 @@ def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
     if save is not None:
         save.sc1, save.sh1 = sc, sh
     pair = None
-    if r.ws3 is not None and x.dtype == torch.float32 and RAW_PAIR_FUSED:
+    direct = _a32_shortcut(r, x, skip, save)                  # the shortcut GEMM splits x | skip itself: no pair to write here
+    if r.ws3 is not None and x.dtype == torch.float32 and RAW_PAIR_FUSED and not direct:
         # mixed scheme: the shortcut's split operand [hi | lo] of (x | skip) comes out of the same pass as norm1 + SiLU
         y, pair = ops.scale_shift_act(x, skip, n, hw, sc, sh, 1, out_dtype=r.dtype, raw_pair=True)
     else:
@@ -476,9 +502,12 @@ def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
         save.h1, save.sc2, save.sh2 = h1, sc, sh
     y2 = ops.scale_shift_act(h1, None, n, h * wp, sc, sh, 1, out_dtype=r.dtype)
     if r.ws3 is not None:         # mixed scheme: the shortcut maps the stream linearly -> split precision, fp32 out
-        if pair is None:
-            pair = split_operand(x, skip, dtype=r.dtype)
-        short = exact_gemm(pair, r.ws3, r.cout, w_in=n * hw, bias=r.bs, out_dtype=r.stream)
+        if direct:
+            short = exact_gemm_f32(x, r.ws3, r.cout, r.dtype, x1=skip, w_in=n * hw, bias=r.bs, out_dtype=r.stream)
+        else:
+            if pair is None:
+                pair = split_operand(x, skip, dtype=r.dtype)
+            short = exact_gemm(pair, r.ws3, r.cout, w_in=n * hw, bias=r.bs, out_dtype=r.stream)
     elif r.ws is not None:
         short = ops.conv_gemm(x, r.ws, r.cout, a1=skip, n_img=n, h_in=h, w_in=w, ksize=1, bias=r.bs)
     else:
@@ -552,8 +581,7 @@ def run_transformer(t, x, text, kv=None, split=None):
     hw = h * w
     sc, sh = ops.groupnorm_scale_shift(x, None, n, hw, t.norm.groups, t.norm.eps, t.norm.g, t.norm.b)
     if t.w_in3 is not None:       # mixed scheme: proj_in / proj_out carry the stream -> split precision
-        tok = exact_gemm(split_operand(x, None, sc, sh, 0, dtype=t.dtype), t.w_in3, Cc, w_in=n * hw, bias=t.b_in,
-                         out_dtype=t.stream)
+        tok = exact_gemm_f32(x, t.w_in3, Cc, t.dtype, scale=sc, shift=sh, w_in=n * hw, bias=t.b_in, out_dtype=t.stream)
     else:
         y = ops.scale_shift_act(x, None, n, hw, sc, sh, 0)
         tok = ops.linear(y.view(n * hw, Cc), t.w_in, bias=t.b_in)

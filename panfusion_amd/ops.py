@@ -553,7 +553,8 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
               bias=None, rowvec=None, residual=None, out=None, out_dtype=None, batch=1,
               a_bstride=0, w_bstride=0, out_bstride=0, res_bstride=0, a0_ld=None, a1_ld=None, c0=None, c1=None,
               out_ld=None, res_ld=None, geglu=False, algo_k=None, split_out=False, pad_hi=0, gn_stats=False,
-              wrap_pad=0, crop=0, split3=False, plan_only=False, subpixel=False):
+              wrap_pad=0, crop=0, split3=False, plan_only=False, subpixel=False, a32_dtype=None, a_scale=None, a_shift=None,
+              want_plan=False):
     """out[m, n] = sum_k A[m, k] W[n, k] (+bias +rowvec[img] +residual).  a0/a1 NHWC, the last
     dim is the channel stride; returns [M, n_out] (M = n_img * h_out * w_out).  The output takes the
     residual's dtype unless out_dtype says otherwise (fp32 residual stream in, fp32 out).
@@ -567,7 +568,12 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     loses `crop` columns on both sides (unpad_pano): pad -> conv -> crop of the panorama branch without the padded copies.
     subpixel: an upsampling convolution (ksize 3, upsample 1) as four 2x2 phase convolutions on the low-resolution grid; w = engine._subpixel_weight
     ([4 * n_out, 4 * C]): 4 instead of 9 MACs per output value and input channel (pf_conv_desc.subpixel).
-    plan_only: launch nothing, return pf_conv_gemm_kernel_id of the problem (0 / 1: the 16x16x32 tile kernels, 2: the 32x32x16 kernel)."""
+    plan_only: launch nothing, return pf_conv_gemm_kernel_id of the problem (0 / 1: the 16x16x32 tile kernels, 2: the 32x32x16 kernel);
+    want_plan: launch nothing, return the library's plan (ConvPlan) of the launch, with GroupNorm moments if gn_stats.
+    a32_dtype (with split3, ksize 1): a0 / a1 are the fp32 tensors themselves (c0 / c1 fp32 channels) and a32_dtype the 16-bit type of the
+    MFMA operands; the kernel forms the pair [hi | lo] of a0 | a1 (a_scale / a_shift [n_img, c0 + c1]: of their GroupNorm-applied values) while
+    it stages them (pf_conv_desc.a_src_dtype) -- conv_gemm_a32 is the front end."""
+    op_dtype = a32_dtype or a0.dtype                # type of the MFMA operands
     c0 = c0 if c0 is not None else a0.shape[-1]
     c1 = (c1 if c1 is not None else a1.shape[-1]) if a1 is not None else 0
     if w_in is None:
@@ -579,29 +585,30 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     if out is not None:
         out_dtype = out.dtype
     if split_out:
-        out_dtype = a0.dtype
-    out_dtype = out_dtype or (residual.dtype if residual is not None else a0.dtype)
+        out_dtype = op_dtype
+    out_dtype = out_dtype or (residual.dtype if residual is not None else op_dtype)
     n_store = n_out // 2 if geglu else (2 * n_out if split_out else n_out)
-    if out is None:
+    if out is None and not want_plan:                             # (a plan query allocates nothing)
         out = torch.empty((batch, M, n_store) if batch > 1 else (M, n_store), device=a0.device, dtype=out_dtype)
     a0_ld = a0_ld if a0_ld is not None else _ld(a0)
     a1_ld = (a1_ld if a1_ld is not None else _ld(a1)) if a1 is not None else 0
     rowvec_ld = _ld(rowvec) if rowvec is not None else 0
     res_ld = (res_ld if res_ld is not None else _ld(residual)) if residual is not None else 0
-    res_dtype = dt(residual) if residual is not None else dt(a0)
-    out_ld = out_ld if out_ld is not None else _ld(out)
+    res_dtype = dt(residual) if residual is not None else dt(op_dtype)
+    out_ld = out_ld if out_ld is not None else (_ld(out) if out is not None else n_store)
     epilogue = 1 if geglu else (2 if split_out else 0)
     # One descriptor per problem SHAPE, filled once and reused (a launch-bound training step issues ~1500 of these per step:
     # the ~35 scalar members cost more host time than the call); with it the library's plans for the shape, asked once.  Per call
     # only the pointers change.
     pkey = (c0, c1, a0_ld, a1_ld, n_img, h_in, w_in, h_out, w_out, ksize, stride, pad, upsample, n_out, batch, epilogue, wrap_pad,
-            crop, dt(a0), dt(out_dtype), residual is not None, res_dtype, res_ld, rowvec is not None, rowvec_ld, bias is not None,
-            out_ld, a_bstride, w_bstride, out_bstride, res_bstride, bool(split3), bool(subpixel))
+            crop, dt(op_dtype), dt(out_dtype), residual is not None, res_dtype, res_ld, rowvec is not None, rowvec_ld, bias is not None,
+            out_ld, a_bstride, w_bstride, out_bstride, res_bstride, bool(split3), bool(subpixel), PF_F32 if a32_dtype else 0, a_scale is not None)
     plans = _PLANS.plans
     plan = plans.get(pkey)
     if plan is None:
         d = _conv_desc(pkey)
         d.a0, d.a1, d.w, d.bias, d.rowvec, d.residual, d.out = _p(a0), _p(a1), _p(w), _p(bias), _p(rowvec), _p(residual), _p(out)
+        d.a_scale, d.a_shift = _p(a_scale), _p(a_shift)
         if len(plans) >= _PLANS.LIMIT:
             plans.pop(next(iter(plans)))
         plan = plans[pkey] = [d, _conv_plan(d, 0), None]
@@ -609,7 +616,12 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     if plan_only:
         return plan[1].kernel
     d.a0, d.a1, d.w, d.bias, d.rowvec, d.residual, d.out = _p(a0), _p(a1), _p(w), _p(bias), _p(rowvec), _p(residual), _p(out)
+    d.a_scale, d.a_shift = _p(a_scale), _p(a_shift)
     d.gn_partial, d.gn_rows, d.tickets, d.n_tickets = None, 0, None, 0
+    if want_plan:
+        if gn_stats and GN_FROM_EPILOGUE and batch == 1 and plan[2] is None:
+            plan[2] = _conv_plan(d, 1)
+        return plan[2] if gn_stats and GN_FROM_EPILOGUE and batch == 1 and plan[2].gn_rows > 0 else plan[1]
     g, gn = plan[1], None
     if gn_stats and GN_FROM_EPILOGUE and batch == 1:
         if plan[2] is None:
@@ -630,7 +642,7 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     else:
         _traced("k_conv_gemm", 2.0 * M * n_out * (algo_k or ksize * ksize * (c0 + c1)) * batch,
                 lambda: check(_lib.lib().pf_conv_gemm(C.byref(d), _stream()), "pf_conv_gemm"),
-                "M%d N%d K%d k%d s%d u%d b%d%s" % (M, n_out, ksize * ksize * (c0 + c1), ksize, stride, upsample, batch, " g32" if plan[1].kernel == 2 else " subpixel" if subpixel else ""))
+                "M%d N%d K%d k%d s%d u%d b%d%s" % (M, n_out, ksize * ksize * (c0 + c1) * (2 if a32_dtype else 1), ksize, stride, upsample, batch, " g32" if plan[1].kernel == 2 else " subpixel" if subpixel else ""))
     if gn is not None:
         out._pf_gn = gn                      # (a tensor that carries moments must not be written in place afterwards)
     elif hasattr(out, "_pf_gn"):
@@ -638,12 +650,44 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     return out
 
 
+def conv_gemm_a32(x0, w3, n_out, dtype, *, x1=None, scale=None, shift=None, n_img=1, w_in=None, **kw):
+    """Split-precision 1x1 GEMM straight from the fp32 stream: x0 | x1 [.., C0] | [.., C1] fp32 (C0, C1 multiples of 32), optionally
+    GroupNorm-applied (scale / shift [n_img, C0 + C1] of groupnorm_scale_shift; no activation), against w3 = engine._split_weight's
+    [W_hi | W_lo] packing, MFMA operands of type dtype.  The result is bit for bit that of
+    conv_gemm(scale_shift_act(x0, x1, .., split=True), w3, split3=True), without the pair tensor's round trip through memory: the
+    kernels split every K block in registers while they stage it (same tile kernel, same plan, traced as that launch: K = 2 C)."""
+    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
+    if w_in is None:
+        w_in = x0.numel() // (C0 * n_img)
+    return conv_gemm(x0, w3, n_out, a1=x1, n_img=n_img, h_in=1, w_in=w_in, c0=C0, c1=C1 if x1 is not None else None,
+                     algo_k=C0 + C1, split3=True, a32_dtype=dtype, a_scale=scale, a_shift=shift, **kw)
+
+
+def conv_gemm_a32_serves(x0, w3, n_out, dtype, **kw):
+    """Does conv_gemm_a32 serve this problem?  Everything but a GroupNorm-applied source (scale / shift) whose plan is the 256 x 160
+    tile of the 8-wave kernel: its registers do not hold the affine operands (pf_conv_gemm refuses it); that problem keeps the pair form."""
+    if kw.get("scale") is None:
+        return True
+    g = conv_gemm_a32(x0, w3, n_out, dtype, want_plan=True, **kw)     # (the plan cached with the shape's descriptor: nothing is allocated, nothing launched)
+    return not (g.kernel == 1 and g.block_rows == 256 and g.nrep == 5)
+
+
+def a32_ok(x0, x1=None):
+    """Can conv_gemm_a32 take these sources?  fp32, channel counts that are multiples of 32, 16-byte aligned rows."""
+    for t in (x0, x1):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.shape[-1] % 32 or t.stride(-1) != 1 or _ld(t) % 4 or t.data_ptr() % 16 or not t.is_contiguous():
+            return False
+    return True
+
+
 def _conv_desc(pkey):
     """The scalar members of a pf_conv_desc from conv_gemm's problem key (the pointers are the caller's)."""
     d = ConvDesc()
     (d.c0, d.c1, d.a0_ld, d.a1_ld, d.n_img, d.h_in, d.w_in, d.h_out, d.w_out, d.ksize, d.stride, d.pad, d.upsample, d.n_out, d.batch,
      d.epilogue, d.wrap_pad, d.crop, d.dtype, d.out_dtype, _, d.res_dtype, d.res_ld, _, d.rowvec_ld, _, d.out_ld,
-     d.a_bstride, d.w_bstride, d.out_bstride, d.res_bstride, d.split3, d.subpixel) = pkey
+     d.a_bstride, d.w_bstride, d.out_bstride, d.res_bstride, d.split3, d.subpixel, d.a_src_dtype, _) = pkey
     return d
 
 
@@ -664,7 +708,7 @@ def gemm_workspace_bytes(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, k
     h_out = ((h_in << upsample) + 2 * pad - ksize) // stride + 1
     w_out = (((w_in + 2 * wrap_pad) << upsample) + 2 * pad - ksize) // stride + 1 - 2 * crop
     d = _conv_desc((c0, c1, c0, c1, n_img, h_in, w_in, h_out, w_out, ksize, stride, pad, upsample, n_out, batch, 0, wrap_pad, crop,
-                    dt(a0), dt(a0), False, dt(a0), 0, False, 0, False, n_out, 0, 0, 0, 0, False, bool(subpixel)))
+                    dt(a0), dt(a0), False, dt(a0), 0, False, 0, False, n_out, 0, 0, 0, 0, False, bool(subpixel), 0, False))
     d.a1 = _p(a1)
     return max(_conv_plan(d, 0).workspace_bytes, _conv_plan(d, 1).workspace_bytes)
 

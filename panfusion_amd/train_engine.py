@@ -665,7 +665,11 @@ class TrainBranch(engine.Branch):
         if KEEP:
             self.h, rec = transformer_forward_keep(t, x, self.text)
         else:
-            super().attention(t)
+            engine.TAPING = True                  # (the recompute of the backward runs the two-launch form: so does this forward)
+            try:
+                super().attention(t)
+            finally:
+                engine.TAPING = False
         self.tape.append(("attention", self, t, x, rec))
 
     def push(self):
