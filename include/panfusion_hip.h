@@ -526,6 +526,17 @@ pf_status pf_attention(const pf_attn_desc* desc, void* stream);
 /* Bytes of pf_attn_desc.workspace that let pf_attention split the key range of this problem (0: it would not split). */
 size_t pf_attention_workspace_size(const pf_attn_desc* desc);
 
+/* Flash attention at WIDE heads (replaces the mid-block Attention(heads=1, dim_head=C) of diffusers' AutoencoderKL --
+ * baddbmm + softmax + bmm over an N x N score matrix -- reached from models/pano/PanoGenerator.py:213-238):
+ *   out[b][i][h*D + :] = softmax_j(scale * q_i.k_j) v_j      D in {128, 256, 512}, H >= 1
+ * Operand layout and alignment rules of pf_attention (q, k leading dimensions multiples of 8, out / vt of 4, vt_ld >= nk
+ * rounded up to 32, 16-byte aligned pointers, fp16 or bf16).  bias, flags, lse and workspace must be NULL: no bias, no
+ * backward and no key-range split at these widths.  Batch strides are 64-bit; INSIDE one (batch, head) slice K and V^T are
+ * addressed with 31-bit byte offsets, so the per-batch operand limits are (nk + 64) * k_ld * 2 < 2^31 and
+ * D * vt_ld * 2 < 2^31 bytes (16-bit elements); the grid is 1-D: ceil(nq / 64) * H * B < 2^31.  Anything else is
+ * PF_ERR_ARG before any launch. */
+pf_status pf_attention_wide(const pf_attn_desc* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training: backward of the EPA block (reference models/pano/modules.py:15-59 under autograd;
  * models/modules/transformer.py:77-161 -- the reference recomputes the block in backward,

@@ -168,6 +168,7 @@ SIGNATURES = {
                                c_void_p, c_void_p]),
     "pf_attention": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "pf_attention_workspace_size": (c_size_t, [C.POINTER(AttnDesc)]),
+    "pf_attention_wide": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "pf_attention_delta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_long, c_void_p, c_void_p]),
     "pf_attention_bwd": (c_int, [C.POINTER(AttnBwdDesc), c_void_p]),
     "pf_attention_bwd_workspace_size": (c_size_t, [C.POINTER(AttnBwdDesc)]),

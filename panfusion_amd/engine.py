@@ -128,6 +128,34 @@ def _a32_shortcut(r, x, skip, save):
             and ops.a32_ok(x, skip))
 
 
+def row_ranges(rows, row_bytes, max_operand_bytes=(1 << 31) - 1):
+    """The fewest ranges [r0, r1) of `rows` rows of `row_bytes` bytes each, as equal as possible, that cover the rows once and in order
+    with every range at most max_operand_bytes (default: pf_conv_gemm's 2 GiB - 1 of 32-bit byte offsets).  Pure host arithmetic."""
+    if rows <= 0 or row_bytes <= 0 or max_operand_bytes < row_bytes:
+        raise ValueError("row_ranges: %d rows of %d bytes do not fit ranges of %d bytes" % (rows, row_bytes, max_operand_bytes))
+    most = max_operand_bytes // row_bytes
+    k = -(-rows // most)
+    base, extra = divmod(rows, k)
+    out, r0 = [], 0
+    for i in range(k):
+        r1 = r0 + base + (1 if i < extra else 0)
+        out.append((r0, r1))
+        r0 = r1
+    return out
+
+
+def _split_shortcut(r, x, n_rows, max_operand_bytes):
+    """The resnet's 1x1 split-precision shortcut over pixel-row ranges that fit max_operand_bytes: a 1x1 GEMM is independent per pixel
+    row, so each range is the same launch on pointer offsets into the same input and output tensors."""
+    cin = x.shape[-1]
+    x2 = x.view(n_rows, cin)
+    short = torch.empty(n_rows, r.cout, device=x.device, dtype=r.stream)
+    row_bytes = max(cin * x.element_size(), r.cout * short.element_size())     # the fp32 source = its [hi | lo] pair; the output
+    for r0, r1 in row_ranges(n_rows, row_bytes, max_operand_bytes):
+        exact_gemm_f32(x2[r0:r1], r.ws3, r.cout, r.dtype, w_in=r1 - r0, bias=r.bs, out=short[r0:r1], split_k=False)   # (K in one pass: the rows of a range do not decide the summation order)
+    return short
+
+
 def exact_gemm(a_split, w3, n_out, **kw):
     """Split-precision GEMM / conv: a_split [.., 2C] and w3 (per tap) hold, per block of 32 channels, [hi(32) | lo(32)]; every
     64-element K block is multiplied as W_hi A_hi + W_hi A_lo + W_lo A_hi in ONE stage of the kernels (pf_conv_desc.split3:
@@ -183,8 +211,8 @@ def pack_resnet_plain(res, dev, dtype, mixed=False):
     return r
 
 
-def run_resnet_plain(r, x):
-    return run_resnet(r, x, None, None)
+def run_resnet_plain(r, x, max_operand_bytes=None):
+    return run_resnet(r, x, None, None, max_operand_bytes=max_operand_bytes)
 
 
 def _current_lora(attn, name, lin):
@@ -467,7 +495,7 @@ def pack_epa(block, dev, dtype, mixed=False):
 
 
 # ---------------------------------------------------------------------------- layer runners
-def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
+def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None, max_operand_bytes=None):
     """x [n, h, w, C] (+ skip concatenated along channels) -> [n, h, w, cout], stream dtype in and out.
     GN -> SiLU -> conv3x3 (+bias +temb) -> GN -> SiLU -> conv3x3 (+bias) + shortcut(x).
     GroupNorm moments: conv1's epilogue leaves the moments of h1 behind for norm2 (ops.conv_gemm(gn_stats=True)); norm1 uses
@@ -478,7 +506,10 @@ def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
     contaminating the two outermost ones), norm2 normalises exactly that tensor, conv2 produces only the w columns that
     survive the crop, and the 1x1 shortcut / identity acts on the un-padded x.
     save (a namespace, training forward): keeps what the backward reads -- both norms' (scale, shift) and h1, which is then
-    produced in fp32 (the GroupNorm backward wants it at that precision) -- so that nothing is recomputed there."""
+    produced in fp32 (the GroupNorm backward wants it at that precision) -- so that nothing is recomputed there.
+    max_operand_bytes (the VAE at panorama sizes; None = never): a split-precision 1x1 shortcut (r.ws3, mixed scheme) whose fp32 source
+    or output passes it runs over pixel-row ranges (row_ranges).  The 16-bit shortcut of the "fast" scheme (r.ws) is NOT split: its
+    operand is half the size (1.14 GB for the 1024 x 2176 x 256 stream) and a larger one still ends in pf_conv_gemm's size error."""
     n, h, w, _ = x.shape
     hw = h * w
     sc, sh = ops.groupnorm_scale_shift(x, skip, n, hw, r.norm1.groups, r.norm1.eps, r.norm1.g, r.norm1.b,
@@ -487,7 +518,10 @@ def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
         save.sc1, save.sh1 = sc, sh
     pair = None
     direct = _a32_shortcut(r, x, skip, save)                  # the shortcut GEMM splits x | skip itself: no pair to write here
-    if r.ws3 is not None and x.dtype == torch.float32 and RAW_PAIR_FUSED and not direct:
+    # max_operand_bytes (the VAE at panorama sizes; None = never): the shortcut's operand or output passes it -> pixel-row ranges
+    split = (max_operand_bytes is not None and r.ws3 is not None and skip is None and save is None
+             and n * hw * max(x.shape[-1] * x.element_size(), r.cout * 4) > max_operand_bytes)
+    if r.ws3 is not None and x.dtype == torch.float32 and RAW_PAIR_FUSED and not direct and not split:
         # mixed scheme: the shortcut's split operand [hi | lo] of (x | skip) comes out of the same pass as norm1 + SiLU
         y, pair = ops.scale_shift_act(x, skip, n, hw, sc, sh, 1, out_dtype=r.dtype, raw_pair=True)
     else:
@@ -501,7 +535,9 @@ def run_resnet(r, x, skip, temb_all, groups_eps=None, wrap=0, save=None):
     if save is not None:
         save.h1, save.sc2, save.sh2 = h1, sc, sh
     y2 = ops.scale_shift_act(h1, None, n, h * wp, sc, sh, 1, out_dtype=r.dtype)
-    if r.ws3 is not None:         # mixed scheme: the shortcut maps the stream linearly -> split precision, fp32 out
+    if split:
+        short = _split_shortcut(r, x, n * hw, max_operand_bytes)
+    elif r.ws3 is not None:       # mixed scheme: the shortcut maps the stream linearly -> split precision, fp32 out
         if direct:
             short = exact_gemm_f32(x, r.ws3, r.cout, r.dtype, x1=skip, w_in=n * hw, bias=r.bs, out_dtype=r.stream)
         else:

@@ -554,7 +554,7 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
               a_bstride=0, w_bstride=0, out_bstride=0, res_bstride=0, a0_ld=None, a1_ld=None, c0=None, c1=None,
               out_ld=None, res_ld=None, geglu=False, algo_k=None, split_out=False, pad_hi=0, gn_stats=False,
               wrap_pad=0, crop=0, split3=False, plan_only=False, subpixel=False, a32_dtype=None, a_scale=None, a_shift=None,
-              want_plan=False):
+              want_plan=False, split_k=True):
     """out[m, n] = sum_k A[m, k] W[n, k] (+bias +rowvec[img] +residual).  a0/a1 NHWC, the last
     dim is the channel stride; returns [M, n_out] (M = n_img * h_out * w_out).  The output takes the
     residual's dtype unless out_dtype says otherwise (fp32 residual stream in, fp32 out).
@@ -570,6 +570,9 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
     ([4 * n_out, 4 * C]): 4 instead of 9 MACs per output value and input channel (pf_conv_desc.subpixel).
     plan_only: launch nothing, return pf_conv_gemm_kernel_id of the problem (0 / 1: the 16x16x32 tile kernels, 2: the 32x32x16 kernel);
     want_plan: launch nothing, return the library's plan (ConvPlan) of the launch, with GroupNorm moments if gn_stats.
+    split_k = False: no split-K scratch is handed over, so the library reduces K in ONE pass for every output tile (pf_conv_gemm plans without
+    a split when pf_conv_desc.workspace is NULL): the launches of a host-side row split must not let the number of rows decide the
+    summation order (vae.upsample_conv).
     a32_dtype (with split3, ksize 1): a0 / a1 are the fp32 tensors themselves (c0 / c1 fp32 channels) and a32_dtype the 16-bit type of the
     MFMA operands; the kernel forms the pair [hi | lo] of a0 | a1 (a_scale / a_shift [n_img, c0 + c1]: of their GroupNorm-applied values) while
     it stages them (pf_conv_desc.a_src_dtype) -- conv_gemm_a32 is the front end."""
@@ -630,7 +633,7 @@ def conv_gemm(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, ksize=1, str
             g = plan[2]
             gn = (torch.empty(M // g.gn_rows, 2, n_out // 2, device=a0.device, dtype=torch.float32), g.gn_rows)
             d.gn_partial, d.gn_rows = _p(gn[0]), g.gn_rows
-    nbytes = g.workspace_bytes
+    nbytes = g.workspace_bytes if split_k else 0
     ws = torch.empty(nbytes, device=a0.device, dtype=torch.uint8) if nbytes else None   # split-K slabs
     d.workspace, d.workspace_bytes = _p(ws), nbytes
     if nbytes and SPLITK_INKERNEL:
@@ -929,6 +932,29 @@ def attention(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q_bs, 
     _traced("k_attention", 4.0 * B * H * nq * nk * D,
             lambda: check(_lib.lib().pf_attention(C.byref(d), _stream()), "pf_attention"),
             "B%d H%d D%d nq%d nk%d bias%d" % (B, H, D, nq, nk, bias is not None))
+    return out
+
+
+WIDE_HEAD_DIMS = (128, 256, 512)
+
+
+def attention_wide(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q_bs, k_bs, vt_bs, o_bs=None, scale=None, out=None):
+    """Flash attention at head widths 128 / 256 / 512 (pf_attention_wide): the operand layout of `attention`, no bias, no lse."""
+    o_ld = o_ld or H * D
+    o_bs = o_bs if o_bs is not None else nq * o_ld
+    if out is None:
+        out = torch.empty(B, nq, o_ld, device=q.device, dtype=q.dtype)
+    d = AttnDesc()
+    d.q, d.k, d.vt, d.out = _p(q), _p(k), _p(vt), _p(out)
+    d.dtype, d.B, d.H, d.D, d.nq, d.nk = dt(q), B, H, D, nq, nk
+    d.q_ld, d.k_ld, d.vt_ld, d.o_ld = q_ld, k_ld, vt_ld, o_ld
+    d.q_bs, d.k_bs, d.vt_bs, d.o_bs = q_bs, k_bs, vt_bs, o_bs
+    d.scale = scale if scale is not None else D ** -0.5
+    d.bias, d.bias_ld, d.flags, d.flags_ld, d.lse = None, 0, None, 0, None
+    d.workspace, d.workspace_bytes = None, 0
+    _traced("k_attention_wide", 4.0 * B * H * nq * nk * D,
+            lambda: check(_lib.lib().pf_attention_wide(C.byref(d), _stream()), "pf_attention_wide"),
+            "B%d H%d D%d nq%d nk%d" % (B, H, D, nq, nk))
     return out
 
 

@@ -7,11 +7,16 @@ a training step (``PanFusion.py:66-71``, ``PanoGenerator.encode_image``, ``PanoG
 or ``models.vae_params.VAEDecoderParams``), repacks ``post_quant_conv`` + ``decoder`` once into the kernel layouts
 and runs ``decode`` as a sequence of C-ABI calls: the 3x3 convolutions / upsampling convolutions on the MFMA
 implicit-GEMM kernel, GroupNorm + SiLU on the statistics / apply kernels, the 4-channel input convolution and the
-3-channel output convolution on the boundary kernels, and the mid-block attention (ONE head of width 512) as
-two batched GEMMs with a row-softmax kernel in between (its 4096 x 4096 scores per view are materialised in fp32:
-1.3 GB for 20 views -- memory is laid out for 288 GB of HBM, not for a flash kernel at a head width no MFMA
-fragment mapping of ``k_attention_lds`` covers).  Same two storage schemes as the denoiser (engine.py): "mixed"
-(fp32 residual stream, split-precision shortcut convolutions; default for fp16) or "fast".
+3-channel output convolution on the boundary kernels, and the mid-block attention (ONE head of width 512) in one of
+two forms (``attention_plan``): "materialised" -- two batched GEMMs with a row-softmax kernel in between, the
+4096 x 4096 scores per view in fp32 (1.3 GB for 20 views), the query rows cut into chunks where one image's scores
+would pass the GEMM's 2 GiB operand limit -- or "flash" -- ``ops.attention_wide``, the flash kernel for head widths
+128 / 256 / 512 (pf_attention_wide.hip), which holds nothing of size N x N.  The default ("auto") is the materialised
+form, launch for launch what it was at every size that ran before.  Same two storage schemes as the denoiser (engine.py): "mixed"
+(fp32 residual stream, split-precision shortcut convolutions; default for fp16) or "fast".  ``max_operand_bytes`` (default: the
+GEMM's 2 GiB - 1) is the limit of the host-side splits: a resnet's 1x1 shortcut whose operand or output would pass it runs over
+pixel-row ranges (``engine.row_ranges``), an up-sampling convolution over row bands with a one-row halo (``upsample_conv``), both
+bit-identical to the single launch.  With them a 128 x 256 panorama latent (padded: 128 x 272) decodes to 1024 x 2048.
 """
 from types import SimpleNamespace as NS
 
@@ -74,12 +79,77 @@ def pack_vae_decoder(vae, dev, dtype, mixed):
     return v
 
 
-def _attention(att, x, dtype):
+ATTENTION_MODES = ("auto", "materialised", "flash")
+_LIMIT = 1 << 31                       # pf_conv_gemm addresses an operand with 32-bit byte offsets: every operand stays under 2 GiB
+row_ranges = engine.row_ranges         # the pixel-row planner of the host-side splits
+
+
+def _check_mode(mode):
+    if mode not in ATTENTION_MODES:
+        raise ValueError("attention must be one of %s (got %r)" % (", ".join(ATTENTION_MODES), mode))
+    return mode
+
+
+def flash_serves(N, C, dtype):
+    """Does ops.attention_wide (pf_attention_wide) take one head of width C over N tokens in this type?"""
+    return C in ops.WIDE_HEAD_DIMS and dtype in (torch.float16, torch.bfloat16) and (N + 64) * C * 2 < _LIMIT
+
+
+def attention_plan(n, N, C, dtype, mode="auto", max_operand_bytes=_LIMIT - 1):
+    """How the mid-block attention of n images of N tokens (one head of width C, 16-bit type `dtype`) runs.  Pure host arithmetic.
+    Returns a namespace: form "materialised" or "flash"; per = images per pass; rows = query rows per launch of the
+    materialised form (N: the whole image; a smaller multiple of 64: the query rows are cut into chunks so that the fp32
+    scores [rows, N] of a chunk -- and their 16-bit P -- stay under 2 GiB; keys and values stay whole).
+      "materialised": two batched GEMMs around a row softmax over the N x N scores.
+      "flash":        ops.attention_wide, nothing of size N x N; ValueError where the kernel does not serve C or dtype.
+      "auto":         materialised at every size: whole wherever one image's scores fit (N * N * 4 < 2^31: every size that ran before
+                      the flash kernel existed keeps its launches and its bits), query-chunked beyond -- measured on one MI355X at
+                      34 816 tokens the chunked form takes 7.7 ms and the flash kernel 8.8 ms (profiles/wide_attention_ab.txt), so the
+                      default takes the faster one; "flash" is for the caller who wants the 4 GB of transient scores back.
+    max_operand_bytes: the largest GEMM operand (default: the kernel's 2 GiB - 1); a test lowers it to force the chunks at a small size."""
+    _check_mode(mode)
+    limit = max_operand_bytes + 1
+    fits = N * N * 4 < limit
+    if mode == "flash":
+        if not flash_serves(N, C, dtype):
+            raise ValueError("attention='flash' serves head widths %s in fp16 / bf16 (got C = %d, %s, N = %d)"
+                             % (ops.WIDE_HEAD_DIMS, C, dtype, N))
+        return NS(form="flash", per=n, rows=N)
+    if fits:
+        # a few images at a time: the fp32 score matrix of one image is N^2 * 4 bytes (64 MB at 64x64, 340 MB for the
+        # padded 512 x 1088 panorama); 8 of them keep the GEMMs large without holding more than ~2.7 GB
+        return NS(form="materialised", per=min(max(1, min(n, limit // (N * N * 4))), 8), rows=N)
+    most = max_operand_bytes // (N * 4) // 64 * 64         # most query rows whose fp32 scores stay under the limit
+    if most < 64:
+        raise ValueError("VAE attention over %d tokens: 64 rows of fp32 scores exceed %d bytes" % (N, max_operand_bytes))
+    chunks = -(-N // most)
+    return NS(form="materialised", per=1, rows=-(-N // (chunks * 64)) * 64)
+
+
+def materialised_attention(q, k, vt, n, N, Cc, dtype, plan):
+    """softmax(q k^T / sqrt(C)) V0 of n images as two (batched) GEMMs around a row softmax: q, k [n * N, C], vt [n, C, N]
+    (keys contiguous) -> [n * N, C], one piece per pass of `plan` (yielded as (row slice, o) for the caller's epilogue)."""
+    for i0 in range(0, n, plan.per):
+        b = min(plan.per, n - i0)
+        for r0 in range(0, N, plan.rows):
+            R = min(plan.rows, N - r0)
+            rows = slice(i0 * N + r0, i0 * N + r0 + R) if R < N else slice(i0 * N, (i0 + b) * N)
+            keys = slice(i0 * N, (i0 + b) * N)
+            s = ops.conv_gemm(q[rows], k[keys], N, w_in=R, batch=b, a_bstride=N * Cc, w_bstride=N * Cc, out_bstride=R * N,
+                              out_dtype=torch.float32)                     # [b, R, N] = q k^T
+            p = ops.softmax_rows(s.view(b, R, N), Cc ** -0.5, dtype)
+            o = ops.conv_gemm(p.view(b * R, N), vt[i0:i0 + b], Cc, w_in=R, batch=b, a_bstride=R * N, w_bstride=Cc * N,
+                              out_bstride=R * Cc)                          # [b, R, C] = P V0
+            yield rows, o.view(b * R, Cc)
+
+
+def _attention(att, x, dtype, mode="auto", attention_operand_bytes=_LIMIT - 1):
     """diffusers Attention(heads=1, dim_head=C, residual_connection=True) on x [n, h, w, C] (stream dtype)."""
     n, h, w, Cc = x.shape
     N = h * w
     if N % 64:
         raise ValueError("VAE attention needs h*w to be a multiple of 64 (got %dx%d)" % (h, w))
+    plan = attention_plan(n, N, Cc, dtype, mode, attention_operand_bytes)
     sc, sh = ops.groupnorm_scale_shift(x, None, n, N, att.norm.groups, att.norm.eps, att.norm.g, att.norm.b)
     t = ops.scale_shift_act(x, None, n, N, sc, sh, 0, out_dtype=dtype).view(n * N, Cc)
     q = ops.linear(t, att.wq, bias=att.bq)
@@ -87,26 +157,48 @@ def _attention(att, x, dtype):
     vt = ops.linear_t(t.view(n, N, Cc), att.wv, ld=N)                      # [n, C, N]: keys contiguous
     out = torch.empty(n * N, Cc, device=x.device, dtype=x.dtype)
     xs = x.view(n * N, Cc)
-    # a few images at a time: the fp32 score matrix of one image is N^2 * 4 bytes (64 MB at 64x64, 340 MB for the
-    # padded panorama); 8 of them keep the GEMMs large without holding more than ~2.7 GB
-    per = max(1, min(n, (1 << 31) // (N * N * 4))) if N * N * 4 < (1 << 31) else 1
-    per = min(per, 8)
-    for i0 in range(0, n, per):
-        b = min(per, n - i0)
-        rows = slice(i0 * N, (i0 + b) * N)
-        s = ops.conv_gemm(q[rows], k[rows], N, w_in=N, batch=b, a_bstride=N * Cc, w_bstride=N * Cc, out_bstride=N * N,
-                          out_dtype=torch.float32)                         # [b, N, N] = q k^T
-        p = ops.softmax_rows(s.view(b, N, N), Cc ** -0.5, dtype)
-        o = ops.conv_gemm(p.view(b * N, N), vt[i0:i0 + b], Cc, w_in=N, batch=b, a_bstride=N * N, w_bstride=Cc * N,
-                          out_bstride=N * Cc)                              # [b, N, C] = P V0
-        ops.linear(o.view(b * N, Cc), att.wo, bias=att.bo, residual=xs[rows], out=out[rows])
+    if plan.form == "flash":
+        o = ops.attention_wide(q, k, vt, n, 1, Cc, N, N, q_ld=Cc, k_ld=Cc, vt_ld=N, q_bs=N * Cc, k_bs=N * Cc, vt_bs=Cc * N)
+        ops.linear(o.view(n * N, Cc), att.wo, bias=att.bo, residual=xs, out=out)
+    else:
+        for rows, o in materialised_attention(q, k, vt, n, N, Cc, dtype, plan):
+            ops.linear(o, att.wo, bias=att.bo, residual=xs[rows], out=out[rows])
     return out.view(n, h, w, Cc)
 
 
+def upsample_conv(x16, up, out_dtype, max_operand_bytes=_LIMIT - 1):
+    """diffusers Upsample2D (nearest x2 + conv3x3, pad 1) on x16 [n, h, w, C] (16-bit) -> [n, 2h, 2w, up.c] in out_dtype.  One launch
+    where input and output fit max_operand_bytes (every size that ran before); else, image by image, bands of input rows
+    (engine.row_ranges): each band is convolved with a ONE-ROW halo of real input on either side into a scratch band and its
+    interior output rows are copied.  The band launches reduce K in one pass (ops.conv_gemm(split_k=False)): every output value is
+    then the same taps summed in the same order as in a single launch whose plan does not split K -- bit-identical to it.  (A single
+    launch whose plan K-splits the tiles of a badly filled last round -- pf_conv_plan.tail_splits -- sums those rows in another
+    order; none of the VAE's up-sampling convolutions at the sizes that run as one launch has such a plan.)"""
+    n, h, w, Cc = x16.shape
+    osz = torch.empty(0, dtype=out_dtype).element_size()
+    in_row, out_row = w * Cc * x16.element_size(), 2 * (2 * w) * up.c * osz          # bytes per INPUT row: the row, its two output rows
+    if n * h * max(in_row, out_row) <= max_operand_bytes:
+        y = ops.conv_gemm(x16, up.w, up.c, n_img=n, h_in=h, w_in=w, ksize=3, pad=1, upsample=1, bias=up.b, out_dtype=out_dtype)
+        return y.view(n, 2 * h, 2 * w, up.c)
+    out = torch.empty(n, 2 * h, 2 * w, up.c, device=x16.device, dtype=out_dtype)
+    bands = engine.row_ranges(h, max(in_row, out_row), max_operand_bytes - 2 * max(in_row, out_row))   # (room for the two halo rows)
+    for i in range(n):
+        for r0, r1 in bands:
+            a0, a1 = max(r0 - 1, 0), min(r1 + 1, h)
+            y = ops.conv_gemm(x16[i, a0:a1], up.w, up.c, n_img=1, h_in=a1 - a0, w_in=w, ksize=3, pad=1, upsample=1, bias=up.b,
+                              out_dtype=out_dtype, split_k=False).view(2 * (a1 - a0), 2 * w, up.c)
+            out[i, 2 * r0:2 * r1].copy_(y[2 * (r0 - a0):2 * (r1 - a0)])
+    return out
+
+
 class VAEDecoder:
-    def __init__(self, vae, compute_dtype=torch.float16, precision=None):
+    def __init__(self, vae, compute_dtype=torch.float16, precision=None, attention="auto", max_operand_bytes=_LIMIT - 1,
+                 attention_operand_bytes=_LIMIT - 1):
         self.vae, self.compute_dtype = vae, compute_dtype
         self.precision = precision or engine.default_precision(compute_dtype)
+        self.attention = _check_mode(attention)                             # attention_plan's mode
+        self.max_operand_bytes = int(max_operand_bytes)                     # limit of the host-side pixel-row splits (the GEMM's 2 GiB - 1)
+        self.attention_operand_bytes = int(attention_operand_bytes)         # attention_plan's limit (tests lower it to force the query chunks)
         self._packed = {}
 
     def packed(self, device):
@@ -130,24 +222,24 @@ class VAEDecoder:
             # pf_conv_gemm addresses an operand with 32-bit byte offsets (< 2 GiB): the largest one is the split pair
             # [hi | lo] of the second-finest level's width at full resolution (8h x 8w x 2 C1 16-bit values per image)
             per_image = 64 * z.shape[2] * z.shape[3] * 4 * v.c_level1
-            chunk = max(1, ((1 << 31) - 1) // per_image)
+            # (an image that does not fit alone -- the padded 1024 x 2176 panorama -- goes ALONE: its oversize operands are split on the
+            # host, the 1x1 shortcut over pixel-row ranges and the up-sampling convolution over row bands)
+            chunk = max(1, min(self.max_operand_bytes, (1 << 31) - 1) // per_image)
         if n > chunk:
             return torch.cat([self.decode(z[i:i + chunk], chunk) for i in range(0, n, chunk)])
         dt = v.dtype
         # post_quant_conv (1x1 as the centre tap of the 3x3 boundary kernel), then conv_in on its NCHW view
         pq = ops.conv_in(z, v.pq_w, v.pq_b, 8, torch.float32)              # NHWC [n, h, w, 8] fp32
         x = ops.conv_in(ops.nhwc_to_nchw(pq, torch.float32), v.w_in, v.b_in, v.c_top, v.stream)
-        x = engine.run_resnet_plain(v.mid_res[0], x)
-        x = _attention(v.att, x, dt)
-        x = engine.run_resnet_plain(v.mid_res[1], x)
+        x = engine.run_resnet_plain(v.mid_res[0], x, self.max_operand_bytes)
+        x = _attention(v.att, x, dt, self.attention, self.attention_operand_bytes)
+        x = engine.run_resnet_plain(v.mid_res[1], x, self.max_operand_bytes)
         for blk in v.up:
             for r in blk.resnets:
-                x = engine.run_resnet_plain(r, x)
+                x = engine.run_resnet_plain(r, x, self.max_operand_bytes)
             if blk.up is not None:
                 nn_, h, w, Cc = x.shape
-                y = ops.conv_gemm(engine.to16(x, dt), blk.up.w, blk.up.c, n_img=nn_, h_in=h, w_in=w, ksize=3, pad=1, upsample=1,
-                                  bias=blk.up.b, out_dtype=v.stream)
-                x = y.view(nn_, 2 * h, 2 * w, blk.up.c)
+                x = upsample_conv(engine.to16(x, dt), blk.up, v.stream, self.max_operand_bytes)
         nn_, h, w, Cc = x.shape
         sc, sh = ops.groupnorm_scale_shift(x, None, nn_, h * w, v.norm_out.groups, v.norm_out.eps, v.norm_out.g, v.norm_out.b)
         y = ops.scale_shift_act(x, None, nn_, h * w, sc, sh, 1, out_dtype=v.stream).view(nn_, h, w, Cc)
@@ -214,9 +306,13 @@ class VAEEncoder:
     """``vae.encode(x).latent_dist`` on the HIP kernels (the top of every training step, PanFusion.py:66-71):
     ``moments(x)`` -> fp32 NHWC (mean | logvar), ``encode(x)`` -> (mean, logvar) NCHW, ``sample(x, eps)`` -> z."""
 
-    def __init__(self, vae, compute_dtype=torch.float16, precision=None):
+    def __init__(self, vae, compute_dtype=torch.float16, precision=None, attention="auto", max_operand_bytes=_LIMIT - 1,
+                 attention_operand_bytes=_LIMIT - 1):
         self.vae, self.compute_dtype = vae, compute_dtype
         self.precision = precision or engine.default_precision(compute_dtype)
+        self.attention = _check_mode(attention)                             # attention_plan's mode
+        self.max_operand_bytes = int(max_operand_bytes)                     # limit of the host-side pixel-row splits (the GEMM's 2 GiB - 1)
+        self.attention_operand_bytes = int(attention_operand_bytes)         # attention_plan's limit (tests lower it to force the query chunks)
         self._packed = {}
 
     def packed(self, device):
@@ -242,7 +338,7 @@ class VAEEncoder:
         h = ops.conv_in(x, v.w_in, v.b_in, v.c0, v.stream)
         for blk in v.down:
             for r in blk.resnets:
-                h = engine.run_resnet_plain(r, h)
+                h = engine.run_resnet_plain(r, h, self.max_operand_bytes)
             if blk.down is not None:                                        # F.pad(x, (0, 1, 0, 1)) + conv3x3 stride 2, no padding
                 nn_, hh, ww, Cc = h.shape
                 d = blk.down
@@ -252,9 +348,9 @@ class VAEEncoder:
                 else:
                     y = ops.conv_gemm(engine.to16(h, dt), d.w, d.c, out_dtype=v.stream, **kw)
                 h = y.view(nn_, hh // 2, ww // 2, d.c)
-        h = engine.run_resnet_plain(v.mid_res[0], h)
-        h = _attention(v.att, h, dt)
-        h = engine.run_resnet_plain(v.mid_res[1], h)
+        h = engine.run_resnet_plain(v.mid_res[0], h, self.max_operand_bytes)
+        h = _attention(v.att, h, dt, self.attention, self.attention_operand_bytes)
+        h = engine.run_resnet_plain(v.mid_res[1], h, self.max_operand_bytes)
         nn_, hh, ww, Cc = h.shape
         sc, sh = ops.groupnorm_scale_shift(h, None, nn_, hh * ww, v.norm_out.groups, v.norm_out.eps, v.norm_out.g, v.norm_out.b)
         y = ops.scale_shift_act(h, None, nn_, hh * ww, sc, sh, 1, out_dtype=v.stream).view(nn_, hh, ww, Cc)

@@ -1,7 +1,8 @@
 """Time of the VAE decode that follows the sampling loop (PanFusion.py:166-172): 20 view latents 64x64 -> 512^2 images
 and the 64x(128+16) padded panorama latent -> 512x1152 -> crop, SD-2 VAE widths, synthetic weights.
 
-    python tools/vae_bench.py [--dtype fp16|bf16] [--precision mixed|fast] [--reps 3]
+    python tools/vae_bench.py [--dtype fp16|bf16] [--precision mixed|fast] [--reps 3] [--pano-latent 128 256] [--attention auto|materialised|flash]
+(--pano-latent 128 256: the 1024 x 2048 panorama of the two-pass high-resolution sampler, padded to 1024 x 2176)
 """
 import argparse
 import os
@@ -19,6 +20,8 @@ def main():
     ap.add_argument("--precision", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--views", type=int, default=20)
+    ap.add_argument("--pano-latent", type=int, nargs=2, default=(64, 128), metavar=("H", "W"), help="panorama latent size (default 64 128)")
+    ap.add_argument("--attention", default="auto", help="mid-block attention form of the VAE (vae.attention_plan)")
     ap.add_argument("--shapes", action="store_true", help="per-shape table of the decode's GEMM launches (device events, one extra pass)")
     args = ap.parse_args()
     from panfusion_amd import vae as PV
@@ -28,10 +31,11 @@ def main():
     with torch.device(dev):
         params = VAEDecoderParams(**SD2_VAE)
     fill_synthetic(params, 9)
-    dec = PV.VAEDecoder(params, compute_dtype={"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype], precision=args.precision)
+    dec = PV.VAEDecoder(params, compute_dtype={"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype], precision=args.precision, attention=args.attention)
     g = torch.Generator().manual_seed(0)
     lat = torch.randn(1, args.views, 4, 64, 64, generator=g).to(dev)
-    pano = torch.randn(1, 1, 4, 64, 128, generator=g).to(dev)
+    PH, PW = args.pano_latent
+    pano = torch.randn(1, 1, 4, PH, PW, generator=g).to(dev)
     from panfusion_amd import ops
     ops.TRACE = []                                           # algorithmic FLOPs of the decode: summed over its MFMA launches
     PV.decode_views_and_pano(lat, pano, dec)
@@ -43,8 +47,8 @@ def main():
         images, pano_img = PV.decode_views_and_pano(lat, pano, dec)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.reps
-    print("VAE decode of %d views + padded panorama, %s %s: %.1f ms  (%.1f TFLOP in its MFMA launches: %.0f TF/s)  peak memory %.1f GB"
-          % (args.views, args.dtype, dec.precision, dt * 1e3, flop / 1e12, flop / dt / 1e12, torch.cuda.max_memory_allocated() / 2 ** 30))
+    print("VAE decode of %d views + padded %d x %d panorama, %s %s, attention %s: %.1f ms  (%.1f TFLOP in its MFMA launches: %.0f TF/s)  peak memory %.1f GB"
+          % (args.views, 8 * PH, 8 * PW, args.dtype, dec.precision, args.attention, dt * 1e3, flop / 1e12, flop / dt / 1e12, torch.cuda.max_memory_allocated() / 2 ** 30))
     if args.shapes:
         shapes, tot = {}, 0.0
         for name, fl, e0, e1, tag in trace:
@@ -62,9 +66,9 @@ def main():
     with torch.device(dev):
         eparams = VAEEncoderParams(**SD2_VAE)
     fill_synthetic(eparams, 10)
-    enc = PV.VAEEncoder(eparams, compute_dtype={"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype], precision=args.precision)
+    enc = PV.VAEEncoder(eparams, compute_dtype={"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype], precision=args.precision, attention=args.attention)
     imgs = (torch.rand(1, args.views, 3, 256, 256, generator=g) * 2 - 1).to(dev)
-    pano_img = (torch.rand(1, 1, 3, 512, 1024, generator=g) * 2 - 1).to(dev)
+    pano_img = (torch.rand(1, 1, 3, 8 * PH, 8 * PW, generator=g) * 2 - 1).to(dev)
 
     def encode():
         z = PV.encode_image(imgs, enc)
@@ -78,9 +82,9 @@ def main():
         z, zp = encode()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.reps
-    eflop = (args.views * 0.25 + 1152 / 512) * 0.566e12     # ~0.566 TFLOP per 512^2 image through the encoder
-    print("VAE encode of %d views of 256^2 + padded 512x1152 panorama, %s %s: %.1f ms  (~%.0f TF/s algorithmic)  latents %s %s"
-          % (args.views, args.dtype, enc.precision, dt * 1e3, eflop / dt / 1e12, tuple(z.shape), tuple(zp.shape)))
+    eflop = (args.views * 0.25 + 8 * PH * (8 * PW + 128) / 512 ** 2) * 0.566e12     # ~0.566 TFLOP per 512^2 image through the encoder
+    print("VAE encode of %d views of 256^2 + padded %d x %d panorama, %s %s: %.1f ms  (~%.0f TF/s algorithmic)  latents %s %s"
+          % (args.views, 8 * PH, 8 * PW + 128, args.dtype, enc.precision, dt * 1e3, eflop / dt / 1e12, tuple(z.shape), tuple(zp.shape)))
 
 
 if __name__ == "__main__":
