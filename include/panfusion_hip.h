@@ -274,6 +274,48 @@ pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eps_uncond, cons
                                    float* x0_out, const float* known, const float* noise, const float* mask,
                                    float ka, float kb, int known_roll, void* stream);
 
+/* Guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", §3.4; diffusers 0.24
+ * pipeline_stable_diffusion.py: rescale_noise_cfg) applied to the merge of PanoGenerator.py:253-262
+ * (combine_cls_free_guide_pred) on the tensors of PanFusion.py:156-162, one statistic per sample over all of its views, the
+ * panorama a separate one:
+ *   eps = f eps_cfg,  f = phi std(eps_cond) / std(eps_cfg) + 1 - phi = phi sqrt(M2_text / M2_cfg) + 1 - phi,
+ *   M2(v) = sum (v - mean v)^2  (the N - 1 of torch's unbiased std cancels in the ratio and appears nowhere).
+ * pf_cfg_moments is the first of two launches: for each of n_samples samples of sample_elems contiguous fp32 elements it
+ * writes n_partials records of PF_CFG_MOMENT_DOUBLES = 4 float64 sums
+ *   partials[s][p] = (sum c, sum c^2, sum e, sum e^2),  c = eps_cond, e = fmaf(guidance, c - u, u)
+ * -- e is the very fp32 value the update kernels form -- over the elements [p chunk, min((p + 1) chunk, sample_elems)) of
+ * sample s, chunk = ceil(sample_elems / n_partials): a function of (sample_elems, n_partials) alone (an empty range gives
+ * zeros).  mean = sum / N and M2 = sum v^2 - (sum v)^2 / N follow from the records added in index order.  Plain float64 sums:
+ * fp32 squares are exact in float64 and N < 2^31 of them lose < 1e-12 relative, so M2 is good to ~1e-12 (mean / std)^2 --
+ * ample for noise predictions, whose mean is a fraction of their std.  Fixed accumulation order (thread t takes elements
+ * t, t + 256, ... of its chunk, then a butterfly over the lanes and the wavefronts in index order), no atomics: every launch
+ * on the same inputs writes the same bits.  2 <= sample_elems < 2^31, 1 <= n_partials <= PF_CFG_MAX_PARTIALS,
+ * 1 <= n_samples <= 65535; partials: caller-owned, n_samples * n_partials * 4 doubles. */
+#define PF_CFG_MOMENT_DOUBLES 4
+#define PF_CFG_MAX_PARTIALS 256
+pf_status pf_cfg_moments(const float* eps_uncond, const float* eps_cond, float guidance, int n_samples, long sample_elems,
+                         double* partials, int n_partials, void* stream);
+
+/* The second launch: pf_cfg_inpaint_step_pair's update on the rescaled prediction.  known / noise / mask are given together or
+ * are NULL together (NULL: no blend -- pf_cfg_ddim_step_pair with x0_out == NULL, pf_cfg_dpmpp_step_pair otherwise).  The block
+ * of row r adds the n_partials records of sample r / sample_rows in index order in float64, forms
+ *   f = (float)(phi sqrt(M2_text / M2_cfg) + (1 - phi)),  N = sample_rows W;   M2_cfg <= 0 (a constant prediction): f = 1
+ * (diffusers returns NaN there), then eps = f * fmaf(guidance, c - u, u) and the operation sequence of the other update
+ * kernels from eps on: x0 (and the 2M history x0_out) is the x0 of the RESCALED eps, as in diffusers, whose scheduler only ever
+ * sees the rescaled prediction.  Every block of a sample runs the same float64 operations on the same records, hence
+ * multiplies by the same bits of f; phi = 0 gives f = 1 exactly and the outputs of the corresponding existing kernel bit for
+ * bit.  factor_out (or NULL): f per sample, rows / sample_rows floats, written by the block of the sample's first row.
+ * Staging, aliasing rules, roll, out2, tstep and the width limits (16384 DDIM form, 8192 2M form) are pf_cfg_inpaint_step_pair's.
+ * Errors name the argument: sample_rows not dividing rows, phi outside [0, 1] or NaN, partials == NULL, n_partials outside
+ * [1, PF_CFG_MAX_PARTIALS], and everything pf_cfg_inpaint_step_pair refuses. */
+pf_status pf_cfg_rescaled_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
+                                    float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
+                                    float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
+                                    int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                    float* x0_out, const float* known, const float* noise, const float* mask,
+                                    float ka, float kb, int known_roll, const double* partials, int n_partials,
+                                    long sample_rows, float phi, float* factor_out, void* stream);
+
 /* The start state of a sampling run in ONE launch (PanFusion.py:30-43,146-149: the noise the loop starts from, its first roll
  * and timestep tensor; PanoGenerator.py:240-251,264-269: the CFG pair [x ; x] and the integer roll), for a start below
  * strength 1 (diffusers' img2img / inpaint pipelines: latents = scheduler.add_noise(image_latents, noise, latent_timestep)) and

@@ -144,6 +144,11 @@ SIGNATURES = {
                                          c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, C.c_int64,
                                          c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                          c_int, c_void_p]),
+    "pf_cfg_moments": (c_int, [c_void_p, c_void_p, c_float, c_int, c_long, c_void_p, c_int, c_void_p]),
+    "pf_cfg_rescaled_step_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
+                                          c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, C.c_int64,
+                                          c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                          c_int, c_void_p, c_int, c_long, c_float, c_void_p, c_void_p]),
     "pf_noised_start_pair": (c_int, [c_void_p, c_void_p, c_float, c_float, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_int, C.c_int64, c_void_p]),
     "pf_upsampled_start_pair": (c_int, [c_void_p, c_void_p, c_float, c_float, c_long, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -553,10 +553,15 @@ __global__ void k_permute(const void* x, int n, int C, long hw, void* y) {
 // ---- CFG + DDIM ------------------------------------------------------------------------------
 // one element of the CFG merge + DDIM update; explicit fused multiply-adds so that both kernels below round identically
 // whatever contraction the compiler would pick per loop copy
-__device__ __forceinline__ float cfg_ddim_value(float x, float u, float c, float g, float sa, float sb, float sap, float sbp) {
-    const float eps = __builtin_fmaf(g, c - u, u);
-    const float x0 = __builtin_fmaf(-sb, eps, x) / sa;
+__device__ __forceinline__ float cfg_eps(float u, float c, float g) { return __builtin_fmaf(g, c - u, u); }
+// the DDIM update of a given eps, x0 returned too (shared by every update kernel below: the guided eps, or the rescaled one of §4.9)
+__device__ __forceinline__ float ddim_value_x0(float x, float eps, float sa, float sb, float sap, float sbp, float& x0) {
+    x0 = __builtin_fmaf(-sb, eps, x) / sa;
     return __builtin_fmaf(sap, x0, sbp * eps);
+}
+__device__ __forceinline__ float cfg_ddim_value(float x, float u, float c, float g, float sa, float sb, float sap, float sbp) {
+    float x0;
+    return ddim_value_x0(x, cfg_eps(u, c, g), sa, sb, sap, sbp, x0);
 }
 
 __global__ void k_cfg_ddim(const float* __restrict__ x, const float* __restrict__ eu,
@@ -600,9 +605,7 @@ __global__ __launch_bounds__(256) void k_cfg_ddim_rows(const float* x, const flo
 // cfg_ddim_value's operation sequence, x0 returned too: a first-order step stays bit-identical to the DDIM kernels
 __device__ __forceinline__ float cfg_ddim_value_x0(float x, float u, float c, float g, float sa, float sb, float sap, float sbp,
                                                    float& x0) {
-    const float eps = __builtin_fmaf(g, c - u, u);
-    x0 = __builtin_fmaf(-sb, eps, x) / sa;
-    return __builtin_fmaf(sap, x0, sbp * eps);
+    return ddim_value_x0(x, cfg_eps(u, c, g), sa, sb, sap, sbp, x0);
 }
 
 // k_cfg_ddim_rows plus the multistep correction x' = DDIM(x, eps) + k (x0 - x0_prev) (x0_prev == NULL: first order, k unused);
@@ -682,6 +685,121 @@ __global__ __launch_bounds__(256) void k_cfg_inpaint_rows(const float* x, const 
     }
     if (tstep && blockIdx.x == 0)
         for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
+}
+
+// ---- guidance rescale (diffusers rescale_noise_cfg, Lin et al. 2023 §3.4) ------------------------
+// eps <- f eps_cfg, f = phi std(eps_c) / std(eps_cfg) + 1 - phi, one f per sample.  Two launches: k_cfg_moments leaves
+// [n_samples][n_partials] records of four float64 sums (PF_CFG_MOMENT_DOUBLES): sum c, sum c^2, sum e, sum e^2 with
+// e = cfg_eps(u, c, g), the very fp32 value the update multiplies.  Record p of a sample covers the elements
+// [p chunk, min((p + 1) chunk, n)), chunk = ceil(n / n_partials): a function of (n, n_partials) alone.  Inside the block
+// thread t adds elements t, t + 256, ... of the chunk in that order, then a fixed butterfly over the 64 lanes and the 4
+// wavefronts in index order: the same bits on every launch, no atomics.  Plain sums in float64 (not Welford): the sums of
+// <= 2^31 fp32 squares lose nothing that the 1e-6 gate on f could see as long as |mean| is not many thousand std.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_cfg_moments(const float* __restrict__ eu, const float* __restrict__ ec, float g,
+                                                     long sample_elems, int n_partials, double* __restrict__ partials) {
+    __shared__ double red[4][4];
+    const long chunk = (sample_elems + n_partials - 1) / n_partials;
+    long lo = static_cast<long>(blockIdx.x) * chunk;
+    lo = lo < sample_elems ? lo : sample_elems;
+    const long hi = lo + chunk < sample_elems ? lo + chunk : sample_elems;
+    const long base = static_cast<long>(blockIdx.y) * sample_elems;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        const float c = ec[base + i];
+        const double cd = c, ed = cfg_eps(eu[base + i], c, g);
+        s[0] += cd;
+        s[1] = fma(cd, cd, s[1]);
+        s[2] += ed;
+        s[3] = fma(ed, ed, s[3]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = wave_sum_f64(s[j]);
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < 4; ++j) red[threadIdx.x >> 6][j] = s[j];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int j = threadIdx.x;
+        partials[(static_cast<long>(blockIdx.y) * n_partials + blockIdx.x) * 4 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+    }
+}
+
+// f of one sample from its records, added in index order in float64: every thread of every block of the sample runs the same
+// operations on the same operands, so all of them multiply by the same bits.  M2 = sum v^2 - (sum v)^2 / n; the n - 1 of torch's
+// unbiased std cancels in std_text / std_cfg and is deliberately absent.  M2_cfg <= 0 (a constant prediction; NaN in diffusers):
+// f = 1.
+__device__ __forceinline__ float rescale_factor(const double* __restrict__ rec, int n_partials, double n, float phi) {
+    // uniform addresses: the records come through the scalar cache, which serves the thousands of blocks that read the same
+    // 2 KB (per-lane loads of them all land on one L2 channel: measured 54 us instead of 6 for the 5120 rows of cfg 2's views);
+    // 8 records are fetched per batch so that a batch costs one load latency, and added in index order
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    int p = 0;
+    for (; p + 8 <= n_partials; p += 8) {
+        double r[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) r[i] = rec[4 * p + i];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) s[i & 3] += r[i];
+    }
+    for (; p < n_partials; ++p)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] += rec[4 * p + j];
+    const double m2_text = fmax(s[1] - s[0] * s[0] / n, 0.0);
+    const double m2_cfg = s[3] - s[2] * s[2] / n;
+    if (!(m2_cfg > 0.0)) return 1.0f;
+    const double p64 = phi;
+    return static_cast<float>(p64 * sqrt(m2_text / m2_cfg) + (1.0 - p64));
+}
+
+// k_cfg_inpaint_rows' staging with eps = f cfg_eps(u, c, g); BLEND = false: no known region (k_cfg_ddim_rows / k_cfg_dpmpp_rows)
+template <bool X0, bool BLEND>
+__global__ __launch_bounds__(256) void k_cfg_rescaled_rows(const float* x, const float* __restrict__ eu,
+                                                           const float* __restrict__ ec, float g, float sa, float sb, float sap,
+                                                           float sbp, const float* x0_prev, float k, const float* __restrict__ known,
+                                                           const float* __restrict__ noise, const float* __restrict__ mask,
+                                                           float ka, float kb, int known_roll, int W, int roll, float* out,
+                                                           float* out2, float* x0_out, long long* tstep, int n_tstep,
+                                                           long long t_next, const double* __restrict__ partials, int n_partials,
+                                                           int sample_rows, float phi, float* factor_out) {
+    extern __shared__ float stage[];
+    float* row = stage;
+    float* row_x0 = stage + W;
+    const int sample = blockIdx.x / sample_rows;
+    const float f = rescale_factor(partials + static_cast<long>(sample) * n_partials * 4, n_partials,
+                                   static_cast<double>(sample_rows) * W, phi);
+    const long base = static_cast<long>(blockIdx.x) * W;
+    for (int w = threadIdx.x; w < W; w += 256) {
+        int wo = w + roll;
+        wo -= wo >= W ? W : 0;
+        const float eps = f * cfg_eps(eu[base + w], ec[base + w], g);
+        float x0;
+        float v = ddim_value_x0(x[base + w], eps, sa, sb, sap, sbp, x0);
+        if (X0) {
+            if (x0_prev) v = __builtin_fmaf(k, x0 - x0_prev[base + w], v);
+            row_x0[wo] = x0;
+        }
+        if (BLEND) {
+            int wk = w - known_roll;
+            wk += wk < 0 ? W : 0;
+            v = known_blend(v, mask[base + wk], known[base + wk], noise[base + wk], ka, kb);
+        }
+        row[wo] = v;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+        if (X0) x0_out[base + w] = row_x0[w];
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
+    if (factor_out && threadIdx.x == 0 && blockIdx.x % sample_rows == 0) factor_out[sample] = f;
 }
 
 // ---- start state of a run (strength < 1 starts and DenoiseLoop.restart) ----------------------------------------
@@ -1600,6 +1718,72 @@ extern "C" pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eu, c
                            ec, g, sa, sb, sap, sbp, nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, nullptr,
                            reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
     PF_CHECK_LAUNCH("pf_cfg_inpaint_step_pair");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_cfg_moments(const float* eu, const float* ec, float g, int n_samples, long sample_elems, double* partials,
+                                    int n_partials, void* stream) {
+    PF_REQUIRE(eu && ec && partials, "pf_cfg_moments: bad arguments (eps_uncond, eps_cond and partials are required)");
+    PF_REQUIRE(n_samples >= 1 && n_samples <= 65535, "pf_cfg_moments: n_samples=%d must lie in [1, 65535]", n_samples);
+    PF_REQUIRE(sample_elems >= 2 && sample_elems < (1L << 31), "pf_cfg_moments: sample_elems=%ld must lie in [2, 2^31)", sample_elems);
+    PF_REQUIRE(n_partials >= 1 && n_partials <= PF_CFG_MAX_PARTIALS, "pf_cfg_moments: n_partials=%d must lie in [1, %d]", n_partials,
+               PF_CFG_MAX_PARTIALS);
+    hipLaunchKernelGGL(k_cfg_moments, dim3(n_partials, n_samples), dim3(256), 0, as_stream(stream), eu, ec, g, sample_elems,
+                       n_partials, partials);
+    PF_CHECK_LAUNCH("pf_cfg_moments");
+    return PF_OK;
+}
+
+extern "C" pf_status pf_cfg_rescaled_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb,
+                                               float sap, float sbp, long rows, int W, int roll, float* out, float* out2,
+                                               int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
+                                               float* x0_out, const float* known, const float* noise, const float* mask,
+                                               float ka, float kb, int known_roll, const double* partials, int n_partials,
+                                               long sample_rows, float phi, float* factor_out, void* stream) {
+    PF_REQUIRE(x && eu && ec && out && rows > 0 && W > 0, "pf_cfg_rescaled_step_pair: bad arguments");
+    const bool blend = known || noise || mask;
+    PF_REQUIRE(!blend || (known && noise && mask),
+               "pf_cfg_rescaled_step_pair: known, noise and mask are given together or NULL together (NULL: no blend)");
+    PF_REQUIRE(partials, "pf_cfg_rescaled_step_pair: partials is required (pf_cfg_moments writes it)");
+    PF_REQUIRE(n_partials >= 1 && n_partials <= PF_CFG_MAX_PARTIALS, "pf_cfg_rescaled_step_pair: n_partials=%d must lie in [1, %d]",
+               n_partials, PF_CFG_MAX_PARTIALS);
+    PF_REQUIRE(sample_rows > 0 && rows % sample_rows == 0, "pf_cfg_rescaled_step_pair: sample_rows=%ld must divide rows=%ld",
+               sample_rows, rows);
+    PF_REQUIRE(phi >= 0.0f && phi <= 1.0f, "pf_cfg_rescaled_step_pair: phi=%g must lie in [0, 1]", static_cast<double>(phi));
+    PF_REQUIRE(x0_out || !x0_prev, "pf_cfg_rescaled_step_pair: x0_prev requires x0_out (x0_out == NULL is the DDIM form)");
+    const int max_w = x0_out ? 8192 : 16384;
+    PF_REQUIRE(rows < (1L << 31) && W <= max_w,
+               "pf_cfg_rescaled_step_pair: rows=%ld must be < 2^31 and W=%d <= %d (one row per block, %s staged in LDS)", rows, W,
+               max_w, x0_out ? "two rows" : "one row");
+    PF_REQUIRE(sample_rows * W >= 2, "pf_cfg_rescaled_step_pair: a sample of sample_rows=%ld x W=%d has fewer than 2 elements",
+               sample_rows, W);
+    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_rescaled_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
+    PF_REQUIRE(!x0_out || (x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2),
+               "pf_cfg_rescaled_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
+    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_rescaled_step_pair: x0_prev must not alias out / out2");
+    if (blend) {
+        const float* ops_in[3] = {known, noise, mask};
+        for (const float* p : ops_in)
+            PF_REQUIRE(p != out && p != out2 && p != x0_out,
+                       "pf_cfg_rescaled_step_pair: known / noise / mask must not alias out, out2 or x0_out (they are read at an offset)");
+    }
+    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_rescaled_step_pair: n_tstep must be positive with tstep");
+    int r = roll % W;
+    if (r < 0) r += W;
+    int kr = known_roll % W;
+    if (kr < 0) kr += W;
+    const size_t lds = (x0_out ? 2 : 1) * static_cast<size_t>(W) * sizeof(float);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu, ec, g, sa, sb, sap,
+                           sbp, x0_out ? x0_prev : nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, x0_out,
+                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next), partials, n_partials,
+                           static_cast<int>(sample_rows), phi, factor_out);
+    };
+    if (x0_out && blend) launch(k_cfg_rescaled_rows<true, true>);
+    else if (x0_out) launch(k_cfg_rescaled_rows<true, false>);
+    else if (blend) launch(k_cfg_rescaled_rows<false, true>);
+    else launch(k_cfg_rescaled_rows<false, false>);
+    PF_CHECK_LAUNCH("pf_cfg_rescaled_step_pair");
     return PF_OK;
 }
 

@@ -498,6 +498,65 @@ def cfg_inpaint_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=N
     return out, x0_out
 
 
+CFG_MOMENT_DOUBLES = 4       # PF_CFG_MOMENT_DOUBLES: (sum c, sum c^2, sum e, sum e^2) per record
+CFG_PARTIALS = 64            # records per sample the loop uses (a launch of 64 blocks per sample; any value in [1, 256] is valid)
+
+
+def cfg_moments(eps_uncond, eps_cond, guidance, *, samples, out=None, n_partials=None):
+    """First launch of guidance rescale: float64 partial sums of eps_cond and of the guided prediction
+    fmaf(g, c - u, u), ``samples`` samples over the leading elements of the two fp32 tensors, ``n_partials`` records each, into
+    ``out`` (float64, (samples, n_partials, 4); allocated when None -- a loop allocates it once and passes it every step).
+    ``n_partials`` defaults to what ``out`` holds, to CFG_PARTIALS without one.  Deterministic: the same inputs give the same bits."""
+    n = eps_cond.numel()
+    assert eps_uncond.numel() == n and n % samples == 0
+    for t in (eps_uncond, eps_cond):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    if n_partials is None:
+        n_partials = CFG_PARTIALS if out is None else out.numel() // (samples * CFG_MOMENT_DOUBLES)
+    if out is None:
+        out = torch.empty(samples, n_partials, CFG_MOMENT_DOUBLES, dtype=torch.float64, device=eps_cond.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == samples * n_partials * CFG_MOMENT_DOUBLES
+    check(_lib.lib().pf_cfg_moments(_p(eps_uncond), _p(eps_cond), float(guidance), int(samples), n // samples, _p(out),
+                                    int(n_partials), _stream()), "pf_cfg_moments")
+    return out
+
+
+def cfg_rescaled_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0,
+                           x0_prev=None, k=0.0, x0_out=None, *, partials, phi, samples=1, factor_out=None,
+                           known=None, noise=None, mask=None, ka=0.0, kb=0.0, known_roll=0):
+    """cfg_inpaint_step_pair on the rescaled prediction eps = f eps_cfg, f = phi std(eps_cond) / std(eps_cfg) + 1 - phi per
+    sample from ``partials`` (cfg_moments' output for the same predictions and guidance; x holds ``samples`` samples of equal
+    size).  ``known`` / ``noise`` / ``mask`` all None: no blend (cfg_ddim_step_pair, or cfg_dpmpp_step_pair with ``x0_out``).
+    ``factor_out`` (fp32, ``samples`` elements, or None) receives f.  Returns (out, x0_out)."""
+    W = x.shape[-1]
+    rows = x.numel() // W
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and (out2 is None or out2.is_contiguous())
+    assert x0_out is None or (x0_out.is_contiguous() and x0_out.dtype == torch.float32 and x0_out.numel() == x.numel())
+    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
+    for t in (known, noise, mask):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel())
+    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    n_partials = 0
+    if partials is not None:
+        assert partials.dtype == torch.float64 and partials.is_contiguous() and samples > 0
+        assert partials.numel() % (samples * CFG_MOMENT_DOUBLES) == 0
+        n_partials = partials.numel() // (samples * CFG_MOMENT_DOUBLES)
+    assert factor_out is None or (factor_out.dtype == torch.float32 and factor_out.is_contiguous() and factor_out.numel() >= samples)
+    sa, sb, sap, sbp = (float(c) for c in coef)
+    opt = lambda t: _p(t) if t is not None else None
+    # (a samples that does not divide rows reaches the entry point as a sample_rows that does not, and is refused there)
+    sample_rows = rows // samples if rows % samples == 0 else rows + 1
+    check(_lib.lib().pf_cfg_rescaled_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
+                                               rows, W, int(roll), _p(out), opt(out2), opt(tstep),
+                                               tstep.numel() if tstep is not None else 0, int(t_next), opt(x0_prev), float(k),
+                                               opt(x0_out), opt(known), opt(noise), opt(mask), float(ka), float(kb),
+                                               int(known_roll), opt(partials), n_partials, sample_rows, float(phi),
+                                               opt(factor_out), _stream()), "pf_cfg_rescaled_step_pair")
+    return out, x0_out
+
+
 def noised_start_pair(z, noise, ka, kb, roll=0, *, out, out2=None, tstep=None, t0=0):
     """The start state of a run in one launch: ``out`` <- ka z + kb noise rolled by ``roll`` along the width
     (``z=None``: the noise itself, a bit-exact rolled copy), ``out2`` a second copy (the CFG pair's other half), ``tstep`` (int64

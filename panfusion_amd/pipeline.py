@@ -286,7 +286,7 @@ class DenoiseLoop:
 
     def __init__(self, model, latents, pano_latent, prompt_embd, pano_prompt_embd, cameras,
                  steps=50, rot_diff=90.0, guidance_scale=9.0, use_graphs=False, pano_layout_cond=None, sampler="ddim",
-                 known=None, strength=1.0, init=None):
+                 known=None, strength=1.0, init=None, guidance_rescale=0.0):
         """latents (1, m, 4, h, w), pano_latent (1, 1, 4, H, W) fp32 on the GPU: the NOISE (init_noise);
         prompt_embd (2, m, L, D) / pano_prompt_embd (2, 1, L, D) = [null ; prompt];
         cameras: dict of (1, m) CPU tensors (FoV, theta, phi in degrees);
@@ -294,8 +294,12 @@ class DenoiseLoop:
         known: a KnownRegion -- inpainting / outpainting (DESIGN.md §4.6);
         strength in (0, 1], init: a SourceLatents -- the run starts from add_noise(init, noise, t_s) and executes the last
         int(steps * strength) steps of the grid; init defaults to the known latents.  At strength 1 the start
-        is the noise itself, with or without init."""
+        is the noise itself, with or without init.
+        guidance_rescale in [0, 1]: diffusers' ``guidance_rescale`` (rescale_noise_cfg), phi of DESIGN.md §4.9 -- the guided
+        prediction is scaled per latent towards the spread of the conditional one; 0 (default) is the loop without it."""
         k, i0 = executed_steps(steps, strength)
+        if not (isinstance(guidance_rescale, (int, float)) and 0.0 <= guidance_rescale <= 1.0):
+            raise ValueError("guidance_rescale %r must be a number in [0, 1]" % (guidance_rescale,))
         if known is not None:
             known.check(latents, pano_latent)
         if init is not None:
@@ -344,6 +348,14 @@ class DenoiseLoop:
         if init is not None:
             self.src_lat, self.src_pano, self.resample = own(init.latents), own(init.pano_latent), init.resample
         self.tstep = torch.empty(2, self.m, dtype=torch.long, device=dev)
+        self.rescale = float(guidance_rescale)
+        self.rescale_factors = None
+        if self.rescale > 0:
+            # per-latent float64 partial sums of the two predictions (ops.cfg_moments) and the factors f of the last step
+            # (views, panorama): allocated here, written by the two extra launches of every step, never read by the host
+            self._moments_lat = torch.empty(1, ops.CFG_PARTIALS, ops.CFG_MOMENT_DOUBLES, dtype=torch.float64, device=dev)
+            self._moments_pano = torch.empty_like(self._moments_lat)
+            self.rescale_factors = torch.ones(2, dtype=torch.float32, device=dev)
         self.use_graphs = use_graphs
         self.graphs = {}
         # layout condition image (1, 1, 3, Hi, Wi) for the panorama ControlNet: rolled with the panorama
@@ -404,7 +416,7 @@ class DenoiseLoop:
         operand buffers) and a new strength.  None keeps the current value.  Captured graphs, EPA tables and pinned text K/V stay
         valid: no buffer a graph reads is allocated and no address changes.  A new source may have another admissible size
         (``SourceLatents(..., resample=)``): the source buffers are operands of the start launch only, so they
-        are re-allocated then.  Not re-armable: steps, sampler, rot_diff, guidance,
+        are re-allocated then.  Not re-armable: steps, sampler, rot_diff, guidance, guidance_rescale,
         prompts, cameras, and whether the loop has known content at all."""
         shape_lat, shape_pano = (1,) + tuple(self.lat.shape[1:]), (1,) + tuple(self.pano.shape[1:])
         like_lat, like_pano = torch.empty(shape_lat, device="meta"), torch.empty(shape_pano, device="meta")
@@ -552,7 +564,9 @@ class DenoiseLoop:
         # halves of the CFG pair; panorama -- update + roll for the next iteration (a block owns whole rows, so in place for any
         # roll), both halves, and the next call's timestep words.
         t_next = t if last else self.timesteps[self.i + 1]
-        if self.known is not None:
+        if self.rescale > 0:
+            self._rescaled_update(eps, pano_eps, coef, last, t_next)
+        elif self.known is not None:
             self._known_update(eps, pano_eps, coef, last, t_next)
         elif self.solver is None:
             ops.cfg_ddim_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:])
@@ -598,6 +612,32 @@ class DenoiseLoop:
                                   out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
                                   **x0["pano"], **blend(self.known_pano, self.noise_pano, self.mask_pano, o))
 
+    def _rescaled_update(self, eps, pano_eps, coef, last, t_next):
+        """guidance_rescale > 0, every form of the update: per latent one launch for the moments of eps_cond and
+        of the guided prediction and one for the update on f eps_cfg -- DDIM or 2M, with the known-region blend of
+        _known_update where the loop has known content.  f stays on the device (rescale_factors: views, panorama)."""
+        x0 = dict(lat={}, pano={})
+        if self.solver is not None:
+            coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
+            second = order == 2
+            x0 = dict(lat=dict(x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat),
+                      pano=dict(x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano))
+        blend = dict(lat={}, pano={})
+        if self.known is not None:
+            ka, kb = (1.0, 0.0) if last else coef[2:]
+            o = (self.i + 1) * self.shift % self.W
+            blend = dict(lat=dict(known=self.known_lat, noise=self.noise_lat, mask=self.mask_lat, ka=ka, kb=kb, known_roll=0),
+                         pano=dict(known=self.known_pano, noise=self.noise_pano, mask=self.mask_pano, ka=ka, kb=kb, known_roll=o))
+        ops.cfg_moments(eps[0], eps[1], self.guidance, samples=1, out=self._moments_lat)
+        ops.cfg_rescaled_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
+                                   partials=self._moments_lat, phi=self.rescale, factor_out=self.rescale_factors[:1],
+                                   **x0["lat"], **blend["lat"])
+        ops.cfg_moments(pano_eps[0], pano_eps[1], self.guidance, samples=1, out=self._moments_pano)
+        ops.cfg_rescaled_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
+                                   out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
+                                   partials=self._moments_pano, phi=self.rescale, factor_out=self.rescale_factors[1:],
+                                   **x0["pano"], **blend["pano"])
+
     def run(self):
         while self.i < len(self.timesteps):
             self.step()
@@ -621,19 +661,22 @@ class HiResLoop:
     arguments); every final dimension is an integer multiple of the base one, views and panorama independently.  Views of the
     same size in both passes (20 x 64 x 64 at 512x1024 -> 1024x2048) are passed through without resampling.
     steps: the base grid; refine_steps: the refine grid (default: steps), of which int(refine_steps * strength) run;
-    resample: "nearest", "bilinear" or "bicubic"; the other arguments as DenoiseLoop takes them, for both passes.
+    resample: "nearest", "bilinear" or "bicubic"; the other arguments (guidance_rescale among them) as DenoiseLoop
+    takes them, for both passes.
     Known regions and layout conditioning are NOT taken here: compose two DenoiseLoops by hand for them, the second with
     init=SourceLatents(..., resample=)."""
 
     def __init__(self, model, base_noise, noise, prompt_embd, pano_prompt_embd, cameras, *, steps=50, refine_steps=None,
-                 strength=0.5, resample="bicubic", sampler="ddim", guidance_scale=9.0, rot_diff=90.0, use_graphs=False):
+                 strength=0.5, resample="bicubic", sampler="ddim", guidance_scale=9.0, rot_diff=90.0, use_graphs=False,
+                 guidance_rescale=0.0):
         refine_steps = steps if refine_steps is None else refine_steps
         self._check_strength(refine_steps, strength)
         self.resample = resample
         # the refine loop's source buffers, at the size base.result() will have: checks the sizes against each other too
         placeholder = SourceLatents(torch.zeros_like(base_noise[0]), torch.zeros_like(base_noise[1]), resample=resample)
         placeholder.check(*noise)
-        common = dict(rot_diff=rot_diff, guidance_scale=guidance_scale, use_graphs=use_graphs, sampler=sampler)
+        common = dict(rot_diff=rot_diff, guidance_scale=guidance_scale, use_graphs=use_graphs, sampler=sampler,
+                      guidance_rescale=guidance_rescale)
         self.base = DenoiseLoop(model, base_noise[0], base_noise[1], prompt_embd, pano_prompt_embd, cameras, steps=steps, **common)
         self.refine = DenoiseLoop(model, noise[0], noise[1], prompt_embd, pano_prompt_embd, cameras, steps=refine_steps,
                                   strength=strength, init=placeholder, **common)

@@ -7,6 +7,7 @@ SD-2-base shapes, hipGraphs, bench.py's model and inputs).
     python tools/sampler_bench.py --strength 0.5       # DDIM at strength 1 / at strength S from a source
     python tools/sampler_bench.py --restart [--profile]  # set-up of another run: new loop + prepare() against restart()
     python tools/sampler_bench.py --hires [--profile]    # two-pass 512x1024 -> 1024x2048 (HiResLoop)
+    python tools/sampler_bench.py --rescale [PHI] [--profile]  # DDIM without / with guidance rescale
 
 Prints one JSON line:
   * ms_per_step -- the loop step (denoiser graph replay + the two update launches) of each sampler, timed after warm-up
@@ -17,6 +18,10 @@ Fewer steps is what 2M is for; whether 2M-20/25 images match DDIM-50 in quality 
 
 With --known: ms_per_step of DDIM without and with a known region (a seeded panorama latent kept on half of the columns, its
 nearest e2p in the views), alternated the same way; --profile then runs 6 steps of each.
+
+With --rescale [PHI] (default 0.7): ms_per_step of DDIM without and with guidance_rescale = PHI -- two more launches per latent
+and step, pf_cfg_moments and pf_cfg_rescaled_step_pair in place of pf_cfg_ddim_step_pair -- alternated the same way; --profile
+then runs 6 steps of each.  Image quality with the rescale is NOT measured (no trained weights).
 
 With --strength S: ms_per_step of DDIM at strength 1 and at strength S (a seeded source panorama latent and its nearest e2p in
 the views; the grid is sized so that both run --warmup + --steps steps), alternated the same way, and time_to_latents_s of the
@@ -58,6 +63,8 @@ def main():
     ap.add_argument("--restart", action="store_true", help="time DenoiseLoop + prepare() against restart() (set-up of another run)")
     ap.add_argument("--hires", action="store_true", help="two-pass cfg 2 -> cfg 4 through HiResLoop (DESIGN.md §4.8)")
     ap.add_argument("--base-steps", type=int, default=50, help="--hires: the DDIM grid of both passes (2M runs 20)")
+    ap.add_argument("--rescale", type=float, nargs="?", const=0.7, default=None,
+                    help="DDIM without / with guidance_rescale (default 0.7) instead of DDIM / 2M")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -96,6 +103,8 @@ def main():
             # a grid on which strength S leaves exactly `steps` executed steps
             n = next(n for n in range(steps, 1001) if min(int(n * args.strength), n) == steps)
             sampler, steps, kw = "ddim", n, dict(strength=args.strength, init=source(5))
+        if sampler == "ddim_rescale":
+            sampler, kw = "ddim", dict(guidance_rescale=args.rescale)
         loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, sampler=sampler, known=kn, **kw)
         loop.prepare()
         return loop
@@ -109,6 +118,8 @@ def main():
     samplers = ("ddim", "ddim_known") if args.known else ("ddim", "dpmpp_2m")
     if args.strength is not None:
         samplers = ("ddim", "ddim_strength")
+    if args.rescale is not None:
+        samplers = ("ddim", "ddim_rescale")
     if args.profile:
         for sampler in samplers:
             loop = make(sampler, 6)
@@ -137,7 +148,7 @@ def main():
     runs = (("ddim_50", "ddim", 50), ("dpmpp_2m_25", "dpmpp_2m", 25), ("dpmpp_2m_20", "dpmpp_2m", 20))
     if args.strength is not None:
         runs = (("ddim_50", "ddim", 50), ("ddim_50_strength_%g" % args.strength, "ddim_strength", 50))
-    for name, sampler, steps in (() if args.known else runs):
+    for name, sampler, steps in (() if args.known or args.rescale is not None else runs):
         if sampler == "ddim_strength":
             loop = DenoiseLoop(model, *inputs, steps=steps, use_graphs=True, strength=args.strength, init=source(5))
             loop.prepare()
@@ -158,6 +169,8 @@ def main():
            "note": "image quality at 20 / 25 steps of 2M vs 50 of DDIM: not measured"}
     if args.strength is not None:
         res["note"] = "image quality at strength %g: not measured" % args.strength
+    if args.rescale is not None:
+        res["note"] = "image quality with guidance_rescale %g: not measured" % args.rescale
     line = json.dumps(res)
     print(line)
     if args.out:
