@@ -228,8 +228,15 @@ pf_status pf_cfg_ddim_step(const float* x, const float* eps_uncond, const float*
 /* The same update as ONE launch per latent with everything the NEXT denoiser call needs (round 5: no torch.cat / copy_ / fill_
  * kernels between two calls of the loop, PanFusion.py:149-162): out may alias x for ANY roll (a block owns whole rows);
  * out2 (or NULL) receives a second copy -- the other half of the CFG pair torch.cat([x] * 2) of PanoGenerator.py:240-251;
- * tstep (or NULL): n_tstep int64 words set to t_next, the timestep tensor of the next call (PanFusion.py:147).
- * W <= 16384; out2 must not alias x / out. */
+ * tstep (or NULL): n_tstep int64 words (n_tstep > 0) set to t_next, the timestep tensor of the next call (PanFusion.py:147).
+ *
+ * The rules of all four pf_cfg_*_step_pair entry points (one kernel, one launcher; each adds operands to the one before it).
+ * Forms: DDIM (x0_out == NULL; x0_prev must be NULL too): one row staged in LDS, W <= 16384; 2M (x0_out != NULL): two rows,
+ * W <= 8192.  rows < 2^31.  One block per row reads its rows in full before it writes them: out may alias x, and x0_out may alias
+ * x0_prev, for any roll.  Nothing else may overlap: out2 must not alias x / out; out must not alias the predictions; x0_out must
+ * not alias x, the predictions, out or out2; x0_prev must not alias out / out2; known / noise / mask (given together or NULL
+ * together) must not alias out, out2 or x0_out -- they are read at an offset.  A call that breaks a rule returns PF_ERR_ARG
+ * before any launch, with a message that names the entry point called and the argument. */
 pf_status pf_cfg_ddim_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
                                 float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                                 float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
@@ -244,9 +251,8 @@ pf_status pf_cfg_ddim_step_pair(const float* x, const float* eps_uncond, const f
  *   out = DDIM(x, eps) + k (x0 - x0_prev),  k = 1/2 alpha_t (1 - e^-h) / r0  (host: float64, passed as fp32)
  * with eps, x0 and DDIM(x, eps) in the operation sequence of pf_cfg_ddim_step_pair, and writes x0 to x0_out[(w + roll) mod W]
  * -- the history rolls with the state, into the frame of the next call.  x0_prev == NULL: a first-order step (k unused, the
- * history not read), out bit-identical to pf_cfg_ddim_step_pair.  Two rows staged in LDS: W <= 8192.  out may alias x and
- * x0_out may alias x0_prev for any roll; x0_out (required) must not alias x, the predictions, out or out2; x0_prev must not
- * alias out / out2.  x0_prev / x0_out fp32, the shape of x. */
+ * history not read), out bit-identical to pf_cfg_ddim_step_pair.  x0_out is required (the 2M form of the rules above);
+ * x0_prev / x0_out fp32, the shape of x. */
 pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
                                  float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                                  float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
@@ -264,9 +270,8 @@ pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eps_uncond, const 
  * Frames: known / noise / mask stay in the caller's frame and are read at column (w - known_roll) mod W -- the panorama passes
  * the sum of the integer rolls its state has gone through before this update (PanoGenerator.py:264-269: (i + 1) shift mod W at
  * step i), the views 0; the blended value is written at (w + roll) mod W as by the other update kernels.
- * One block per row: out may alias x and x0_out may alias x0_prev for any roll.  DDIM form: one row staged in LDS, W <= 16384,
- * x0_prev must be NULL; 2M form: two rows, W <= 8192.  known / noise / mask (required, fp32, the shape of x; the host expands a
- * per-pixel mask over the channels) must not alias out, out2 or x0_out; the other aliasing rules are pf_cfg_dpmpp_step_pair's. */
+ * known / noise / mask are required (fp32, the shape of x; the host expands a per-pixel mask over the channels); either form
+ * of the rules above. */
 pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
                                    float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                                    float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,
@@ -305,9 +310,8 @@ pf_status pf_cfg_moments(const float* eps_uncond, const float* eps_cond, float g
  * sees the rescaled prediction.  Every block of a sample runs the same float64 operations on the same records, hence
  * multiplies by the same bits of f; phi = 0 gives f = 1 exactly and the outputs of the corresponding existing kernel bit for
  * bit.  factor_out (or NULL): f per sample, rows / sample_rows floats, written by the block of the sample's first row.
- * Staging, aliasing rules, roll, out2, tstep and the width limits (16384 DDIM form, 8192 2M form) are pf_cfg_inpaint_step_pair's.
- * Errors name the argument: sample_rows not dividing rows, phi outside [0, 1] or NaN, partials == NULL, n_partials outside
- * [1, PF_CFG_MAX_PARTIALS], and everything pf_cfg_inpaint_step_pair refuses. */
+ * Refused besides what the rules above refuse: sample_rows not dividing rows, a sample of fewer than 2 elements, phi outside
+ * [0, 1] or NaN, partials == NULL, n_partials outside [1, PF_CFG_MAX_PARTIALS]. */
 pf_status pf_cfg_rescaled_step_pair(const float* x, const float* eps_uncond, const float* eps_cond,
                                     float guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                                     float sqrt_1m_a_prev, long rows, int W, int roll, float* out, float* out2,

@@ -577,114 +577,11 @@ __global__ void k_cfg_ddim(const float* __restrict__ x, const float* __restrict_
     out[r * W + wo] = xn;
 }
 
-// Loop-state update in ONE launch (round 5: no torch.cat / copy_ / fill_ kernels between two denoiser calls): one block per row,
-// the row is updated into LDS at its rolled position and leaves in order, so `out` may alias `x` for ANY roll; a second copy
-// `out2` (the CFG pair's other half -- the denoiser reads [x ; x]) and the next step's timestep words ride along.
-__global__ __launch_bounds__(256) void k_cfg_ddim_rows(const float* x, const float* __restrict__ eu,
-                                                       const float* __restrict__ ec, float g, float sa, float sb, float sap,
-                                                       float sbp, int W, int roll, float* out, float* out2,
-                                                       long long* tstep, int n_tstep, long long t_next) {
-    extern __shared__ float row[];
-    const long base = static_cast<long>(blockIdx.x) * W;
-    for (int w = threadIdx.x; w < W; w += 256) {
-        int wo = w + roll;
-        wo -= wo >= W ? W : 0;
-        row[wo] = cfg_ddim_value(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp);
-    }
-    __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
-}
-
-// ---- CFG + DPM-Solver++(2M) ------------------------------------------------------------------
-// cfg_ddim_value's operation sequence, x0 returned too: a first-order step stays bit-identical to the DDIM kernels
-__device__ __forceinline__ float cfg_ddim_value_x0(float x, float u, float c, float g, float sa, float sb, float sap, float sbp,
-                                                   float& x0) {
-    return ddim_value_x0(x, cfg_eps(u, c, g), sa, sb, sap, sbp, x0);
-}
-
-// k_cfg_ddim_rows plus the multistep correction x' = DDIM(x, eps) + k (x0 - x0_prev) (x0_prev == NULL: first order, k unused);
-// the state row and the x0 row are staged in LDS at their rolled positions, so out may alias x and x0_out may alias x0_prev
-// for ANY roll (every block reads its rows in full before the barrier and writes them after it)
-__global__ __launch_bounds__(256) void k_cfg_dpmpp_rows(const float* x, const float* __restrict__ eu,
-                                                        const float* __restrict__ ec, float g, float sa, float sb, float sap,
-                                                        float sbp, const float* x0_prev, float k, int W, int roll, float* out,
-                                                        float* out2, float* x0_out, long long* tstep, int n_tstep,
-                                                        long long t_next) {
-    extern __shared__ float stage[];
-    float* row = stage;
-    float* row_x0 = stage + W;
-    const long base = static_cast<long>(blockIdx.x) * W;
-    for (int w = threadIdx.x; w < W; w += 256) {
-        int wo = w + roll;
-        wo -= wo >= W ? W : 0;
-        float x0;
-        float v = cfg_ddim_value_x0(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp, x0);
-        if (x0_prev) v = __builtin_fmaf(k, x0 - x0_prev[base + w], v);
-        row[wo] = v;
-        row_x0[wo] = x0;
-    }
-    __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-        x0_out[base + w] = row_x0[w];
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
-}
-
-// ---- CFG + DDIM / DPM-Solver++(2M) with a known region (inpainting / outpainting) ------------------------------
-// k_cfg_ddim_rows (X0 = false) / k_cfg_dpmpp_rows (X0 = true) with diffusers' StableDiffusionInpaintPipeline blend after the
-// update: v <- m v + (1 - m) (ka z + kb n).  z / n / m stay in the caller's frame and are read at column (w - known_roll) mod W
-// (known_roll in [0, W)); m = 1 leaves v unchanged, m = 0 with (ka, kb) = (1, 0) gives z, bit for bit (finite operands).
+// ---- known region (inpainting / outpainting) --------------------------------------------------
+// diffusers' StableDiffusionInpaintPipeline blend after the update: v <- m v + (1 - m) (ka z + kb n).  m = 1 leaves v unchanged,
+// m = 0 with (ka, kb) = (1, 0) gives z, bit for bit (finite operands).
 __device__ __forceinline__ float known_blend(float v, float m, float z, float n, float ka, float kb) {
     return __builtin_fmaf(m, v, (1.0f - m) * __builtin_fmaf(ka, z, kb * n));
-}
-
-template <bool X0>
-__global__ __launch_bounds__(256) void k_cfg_inpaint_rows(const float* x, const float* __restrict__ eu,
-                                                          const float* __restrict__ ec, float g, float sa, float sb, float sap,
-                                                          float sbp, const float* x0_prev, float k, const float* __restrict__ known,
-                                                          const float* __restrict__ noise, const float* __restrict__ mask,
-                                                          float ka, float kb, int known_roll, int W, int roll, float* out,
-                                                          float* out2, float* x0_out, long long* tstep, int n_tstep,
-                                                          long long t_next) {
-    extern __shared__ float stage[];
-    float* row = stage;
-    float* row_x0 = stage + W;
-    const long base = static_cast<long>(blockIdx.x) * W;
-    for (int w = threadIdx.x; w < W; w += 256) {
-        int wo = w + roll;
-        wo -= wo >= W ? W : 0;
-        int wk = w - known_roll;
-        wk += wk < 0 ? W : 0;
-        float v;
-        if (X0) {
-            float x0;
-            v = cfg_ddim_value_x0(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp, x0);
-            if (x0_prev) v = __builtin_fmaf(k, x0 - x0_prev[base + w], v);
-            row_x0[wo] = x0;
-        } else {
-            v = cfg_ddim_value(x[base + w], eu[base + w], ec[base + w], g, sa, sb, sap, sbp);
-        }
-        row[wo] = known_blend(v, mask[base + wk], known[base + wk], noise[base + wk], ka, kb);
-    }
-    __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-        if (X0) x0_out[base + w] = row_x0[w];
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
 }
 
 // ---- guidance rescale (diffusers rescale_noise_cfg, Lin et al. 2023 §3.4) ------------------------
@@ -756,27 +653,55 @@ __device__ __forceinline__ float rescale_factor(const double* __restrict__ rec, 
     return static_cast<float>(p64 * sqrt(m2_text / m2_cfg) + (1.0 - p64));
 }
 
-// k_cfg_inpaint_rows' staging with eps = f cfg_eps(u, c, g); BLEND = false: no known region (k_cfg_ddim_rows / k_cfg_dpmpp_rows)
-template <bool X0, bool BLEND>
-__global__ __launch_bounds__(256) void k_cfg_rescaled_rows(const float* x, const float* __restrict__ eu,
-                                                           const float* __restrict__ ec, float g, float sa, float sb, float sap,
-                                                           float sbp, const float* x0_prev, float k, const float* __restrict__ known,
-                                                           const float* __restrict__ noise, const float* __restrict__ mask,
-                                                           float ka, float kb, int known_roll, int W, int roll, float* out,
-                                                           float* out2, float* x0_out, long long* tstep, int n_tstep,
-                                                           long long t_next, const double* __restrict__ partials, int n_partials,
-                                                           int sample_rows, float phi, float* factor_out) {
+// ---- loop-state update: CFG + DDIM / DPM-Solver++(2M), known region, guidance rescale ---------------------------
+// The end of every row-staged kernel below: the staged row leaves LDS in order to `out` and to the optional second copy `out2`
+// (the CFG pair's other half -- the denoiser reads [x ; x]), under X0 the staged x0 row to `x0_out` with it, and block 0 writes
+// the next call's timestep words.
+template <bool X0>
+__device__ __forceinline__ void store_row_and_tstep(const float* row, const float* row_x0, long base, int W, float* out, float* out2,
+                                                    float* x0_out, long long* tstep, int n_tstep, long long t) {
+    for (int w = threadIdx.x; w < W; w += 256) {
+        const float v = row[w];
+        out[base + w] = v;
+        if (out2) out2[base + w] = v;
+        if (X0) x0_out[base + w] = row_x0[w];
+    }
+    if (tstep && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t;
+}
+
+// Loop-state update in ONE launch (no torch.cat / copy_ / fill_ kernels between two denoiser calls): one block per row, the row
+// is updated into LDS at its rolled position and leaves in order, so `out` may alias `x` for ANY roll (every block reads its rows
+// in full before the barrier and writes them after it).  Per element, in this order:
+//   eps = cfg_eps(u, c, g);  RESCALE: eps <- f eps, f = rescale_factor of the row's sample (the other forms do not multiply by 1)
+//   v = DDIM(x, eps), x0 with it
+//   X0 (the 2M form): v <- v + k (x0 - x0_prev) unless x0_prev == NULL (first order, k unused); x0 is staged in a second LDS row
+//     and leaves to x0_out, which may therefore alias x0_prev
+//   BLEND: v <- known_blend(v, ...), z / n / m stay in the caller's frame and are read at column (w - known_roll) mod W
+//     (known_roll in [0, W))
+// A feature that is off costs nothing: its operands are never read.  Every form is the flat k_cfg_ddim's operation sequence.
+template <bool X0, bool BLEND, bool RESCALE>
+__global__ __launch_bounds__(256) void k_cfg_step_rows(const float* x, const float* __restrict__ eu,
+                                                       const float* __restrict__ ec, float g, float sa, float sb, float sap,
+                                                       float sbp, const float* x0_prev, float k, const float* __restrict__ known,
+                                                       const float* __restrict__ noise, const float* __restrict__ mask,
+                                                       float ka, float kb, int known_roll, int W, int roll, float* out,
+                                                       float* out2, float* x0_out, long long* tstep, int n_tstep,
+                                                       long long t_next, const double* __restrict__ partials, int n_partials,
+                                                       int sample_rows, float phi, float* factor_out) {
     extern __shared__ float stage[];
     float* row = stage;
     float* row_x0 = stage + W;
-    const int sample = blockIdx.x / sample_rows;
-    const float f = rescale_factor(partials + static_cast<long>(sample) * n_partials * 4, n_partials,
-                                   static_cast<double>(sample_rows) * W, phi);
+    const int sample = RESCALE ? blockIdx.x / sample_rows : 0;
+    const float f = RESCALE ? rescale_factor(partials + static_cast<long>(sample) * n_partials * 4, n_partials,
+                                             static_cast<double>(sample_rows) * W, phi)
+                            : 1.0f;
     const long base = static_cast<long>(blockIdx.x) * W;
     for (int w = threadIdx.x; w < W; w += 256) {
         int wo = w + roll;
         wo -= wo >= W ? W : 0;
-        const float eps = f * cfg_eps(eu[base + w], ec[base + w], g);
+        float eps = cfg_eps(eu[base + w], ec[base + w], g);
+        if (RESCALE) eps = f * eps;
         float x0;
         float v = ddim_value_x0(x[base + w], eps, sa, sb, sap, sbp, x0);
         if (X0) {
@@ -791,21 +716,14 @@ __global__ __launch_bounds__(256) void k_cfg_rescaled_rows(const float* x, const
         row[wo] = v;
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-        if (X0) x0_out[base + w] = row_x0[w];
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t_next;
-    if (factor_out && threadIdx.x == 0 && blockIdx.x % sample_rows == 0) factor_out[sample] = f;
+    store_row_and_tstep<X0>(row, row_x0, base, W, out, out2, x0_out, tstep, n_tstep, t_next);
+    if (RESCALE && factor_out && threadIdx.x == 0 && blockIdx.x % sample_rows == 0) factor_out[sample] = f;
 }
 
 // ---- start state of a run (strength < 1 starts and DenoiseLoop.restart) ----------------------------------------
 // out[(w + roll) mod W] = add_noise(z, n, t_s) = fmaf(ka, z, kb * n) -- known_blend's r, so a kept pixel of a known loop starts on
 // the value the blend would write -- or n itself (z == NULL, a bit-exact rolled copy), to both halves of the CFG pair, plus the
-// first call's timestep words: k_cfg_ddim_rows' staging (one block per row, the row leaves LDS in order), written into buffers
+// first call's timestep words: k_cfg_step_rows' staging (one block per row, the row leaves LDS in order), written into buffers
 // that live graphs read.  Latency-bound (1.4 MB at cfg 2): no bandwidth tuning.
 __global__ __launch_bounds__(256) void k_noised_start_rows(const float* __restrict__ z, const float* __restrict__ noise,
                                                            float ka, float kb, int W, int roll, float* __restrict__ out,
@@ -820,13 +738,7 @@ __global__ __launch_bounds__(256) void k_noised_start_rows(const float* __restri
         row[wo] = z ? __builtin_fmaf(ka, z[base + w], kb * n) : n;
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t0;
+    store_row_and_tstep<false>(row, nullptr, base, W, out, out2, nullptr, tstep, n_tstep, t0);
 }
 
 // ---- start state from a SMALLER source (two-pass high-resolution sampling) ----------------------
@@ -914,13 +826,7 @@ __global__ __launch_bounds__(256) void k_upsampled_start_rows(const float* __res
         row[wo] = noise ? __builtin_fmaf(ka, r, kb * noise[base + w]) : r;
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < W; w += 256) {
-        const float v = row[w];
-        out[base + w] = v;
-        if (out2) out2[base + w] = v;
-    }
-    if (tstep && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < n_tstep; i += 256) tstep[i] = t0;
+    store_row_and_tstep<false>(row, nullptr, base, W, out, out2, nullptr, tstep, n_tstep, t0);
 }
 
 // ---- token + position embedding gather (CLIP text encoder, transformers CLIPTextEmbeddings) -------------
@@ -1648,39 +1554,70 @@ extern "C" pf_status pf_cfg_ddim_step(const float* x, const float* eu, const flo
     return PF_OK;
 }
 
+// The one launcher behind the four pf_cfg_*_step_pair entry points (`who` names the one that was called): everything they check
+// alike, the roll normalisation and the choice of k_cfg_step_rows' instantiation -- x0_out: the 2M form, known / noise / mask:
+// the blend, partials: the rescale.  What an entry point REQUIRES it checks itself before it comes here.
+static pf_status cfg_step_pair(const char* who, const float* x, const float* eu, const float* ec, float g, float sa, float sb,
+                               float sap, float sbp, long rows, int W, int roll, float* out, float* out2, int64_t* tstep,
+                               int n_tstep, int64_t t_next, const float* x0_prev, float k, float* x0_out, const float* known,
+                               const float* noise, const float* mask, float ka, float kb, int known_roll, const double* partials,
+                               int n_partials, long sample_rows, float phi, float* factor_out, void* stream) {
+    PF_REQUIRE(x && eu && ec && out && rows > 0 && W > 0, "%s: bad arguments", who);
+    const bool blend = known || noise || mask;
+    PF_REQUIRE(!blend || (known && noise && mask), "%s: known, noise and mask are given together or NULL together (NULL: no blend)", who);
+    PF_REQUIRE(x0_out || !x0_prev, "%s: x0_prev requires x0_out (x0_out == NULL is the DDIM form)", who);
+    const int max_w = x0_out ? 8192 : 16384;
+    PF_REQUIRE(rows < (1L << 31) && W <= max_w, "%s: rows=%ld must be < 2^31 and W=%d <= %d (one row per block, %s staged in LDS)",
+               who, rows, W, max_w, x0_out ? "two rows" : "one row");
+    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec,
+               "%s: out2 must be a buffer of its own, out must not alias the predictions", who);
+    PF_REQUIRE(!x0_out || (x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2),
+               "%s: x0_out must not alias x, the predictions, out or out2 (only x0_prev)", who);
+    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "%s: x0_prev must not alias out / out2", who);
+    if (blend)
+        for (const float* p : {known, noise, mask})
+            PF_REQUIRE(p != out && p != out2 && p != x0_out,
+                       "%s: known / noise / mask must not alias out, out2 or x0_out (they are read at an offset)", who);
+    PF_REQUIRE(!tstep || n_tstep > 0, "%s: n_tstep must be positive with tstep", who);
+    int r = roll % W;
+    if (r < 0) r += W;
+    int kr = known_roll % W;
+    if (kr < 0) kr += W;
+    const size_t lds = (x0_out ? 2 : 1) * static_cast<size_t>(W) * sizeof(float);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu, ec, g, sa, sb, sap,
+                           sbp, x0_prev, k, known, noise, mask, ka, kb, kr, W, r, out, out2, x0_out,
+                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next), partials, n_partials,
+                           static_cast<int>(sample_rows), phi, factor_out);
+    };
+    switch ((x0_out ? 4 : 0) | (blend ? 2 : 0) | (partials ? 1 : 0)) {
+        case 0: launch(k_cfg_step_rows<false, false, false>); break;
+        case 1: launch(k_cfg_step_rows<false, false, true>); break;
+        case 2: launch(k_cfg_step_rows<false, true, false>); break;
+        case 3: launch(k_cfg_step_rows<false, true, true>); break;
+        case 4: launch(k_cfg_step_rows<true, false, false>); break;
+        case 5: launch(k_cfg_step_rows<true, false, true>); break;
+        case 6: launch(k_cfg_step_rows<true, true, false>); break;
+        default: launch(k_cfg_step_rows<true, true, true>); break;
+    }
+    PF_CHECK_LAUNCH(who);
+    return PF_OK;
+}
+
 extern "C" pf_status pf_cfg_ddim_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb, float sap,
                                            float sbp, long rows, int W, int roll, float* out, float* out2,
                                            int64_t* tstep, int n_tstep, int64_t t_next, void* stream) {
-    PF_REQUIRE(x && eu && ec && out && rows > 0 && W > 0, "pf_cfg_ddim_step_pair: bad arguments");
-    PF_REQUIRE(rows < (1L << 31) && W <= 16384, "pf_cfg_ddim_step_pair: rows=%ld must be < 2^31 and W=%d <= 16384 (one row per block, staged in LDS)", rows, W);
-    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_ddim_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
-    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_ddim_step_pair: n_tstep must be positive with tstep");
-    int r = roll % W;
-    if (r < 0) r += W;
-    hipLaunchKernelGGL(k_cfg_ddim_rows, dim3(static_cast<unsigned>(rows)), dim3(256), static_cast<size_t>(W) * sizeof(float), as_stream(stream),
-                       x, eu, ec, g, sa, sb, sap, sbp, W, r, out, out2, reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
-    PF_CHECK_LAUNCH("pf_cfg_ddim_step_pair");
-    return PF_OK;
+    return cfg_step_pair("pf_cfg_ddim_step_pair", x, eu, ec, g, sa, sb, sap, sbp, rows, W, roll, out, out2, tstep, n_tstep, t_next,
+                         nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, 1, 0.f, nullptr, stream);
 }
 
 extern "C" pf_status pf_cfg_dpmpp_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb, float sap,
                                             float sbp, long rows, int W, int roll, float* out, float* out2,
                                             int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
                                             float* x0_out, void* stream) {
-    PF_REQUIRE(x && eu && ec && out && x0_out && rows > 0 && W > 0, "pf_cfg_dpmpp_step_pair: bad arguments (x0_out is required)");
-    PF_REQUIRE(rows < (1L << 31) && W <= 8192, "pf_cfg_dpmpp_step_pair: rows=%ld must be < 2^31 and W=%d <= 8192 (one row per block, two rows staged in LDS)", rows, W);
-    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_dpmpp_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
-    PF_REQUIRE(x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2,
-               "pf_cfg_dpmpp_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
-    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_dpmpp_step_pair: x0_prev must not alias out / out2");
-    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_dpmpp_step_pair: n_tstep must be positive with tstep");
-    int r = roll % W;
-    if (r < 0) r += W;
-    hipLaunchKernelGGL(k_cfg_dpmpp_rows, dim3(static_cast<unsigned>(rows)), dim3(256), 2 * static_cast<size_t>(W) * sizeof(float),
-                       as_stream(stream), x, eu, ec, g, sa, sb, sap, sbp, x0_prev, k, W, r, out, out2, x0_out,
-                       reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
-    PF_CHECK_LAUNCH("pf_cfg_dpmpp_step_pair");
-    return PF_OK;
+    PF_REQUIRE(x0_out, "pf_cfg_dpmpp_step_pair: bad arguments (x0_out is required)");
+    return cfg_step_pair("pf_cfg_dpmpp_step_pair", x, eu, ec, g, sa, sb, sap, sbp, rows, W, roll, out, out2, tstep, n_tstep, t_next,
+                         x0_prev, k, x0_out, nullptr, nullptr, nullptr, 0.f, 0.f, 0, nullptr, 0, 1, 0.f, nullptr, stream);
 }
 
 extern "C" pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eu, const float* ec, float g, float sa, float sb,
@@ -1688,37 +1625,9 @@ extern "C" pf_status pf_cfg_inpaint_step_pair(const float* x, const float* eu, c
                                               int64_t* tstep, int n_tstep, int64_t t_next, const float* x0_prev, float k,
                                               float* x0_out, const float* known, const float* noise, const float* mask,
                                               float ka, float kb, int known_roll, void* stream) {
-    PF_REQUIRE(x && eu && ec && out && known && noise && mask && rows > 0 && W > 0,
-               "pf_cfg_inpaint_step_pair: bad arguments (known, noise and mask are required)");
-    PF_REQUIRE(x0_out || !x0_prev, "pf_cfg_inpaint_step_pair: x0_prev requires x0_out (x0_out == NULL is the DDIM form)");
-    const int max_w = x0_out ? 8192 : 16384;
-    PF_REQUIRE(rows < (1L << 31) && W <= max_w,
-               "pf_cfg_inpaint_step_pair: rows=%ld must be < 2^31 and W=%d <= %d (one row per block, %s staged in LDS)", rows, W,
-               max_w, x0_out ? "two rows" : "one row");
-    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_inpaint_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
-    PF_REQUIRE(!x0_out || (x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2),
-               "pf_cfg_inpaint_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
-    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_inpaint_step_pair: x0_prev must not alias out / out2");
-    const float* ops_in[3] = {known, noise, mask};
-    for (const float* p : ops_in)
-        PF_REQUIRE(p != out && p != out2 && p != x0_out,
-                   "pf_cfg_inpaint_step_pair: known / noise / mask must not alias out, out2 or x0_out (they are read at an offset)");
-    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_inpaint_step_pair: n_tstep must be positive with tstep");
-    int r = roll % W;
-    if (r < 0) r += W;
-    int kr = known_roll % W;
-    if (kr < 0) kr += W;
-    const size_t lds = (x0_out ? 2 : 1) * static_cast<size_t>(W) * sizeof(float);
-    if (x0_out)
-        hipLaunchKernelGGL(k_cfg_inpaint_rows<true>, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu, ec,
-                           g, sa, sb, sap, sbp, x0_prev, k, known, noise, mask, ka, kb, kr, W, r, out, out2, x0_out,
-                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
-    else
-        hipLaunchKernelGGL(k_cfg_inpaint_rows<false>, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu,
-                           ec, g, sa, sb, sap, sbp, nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, nullptr,
-                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next));
-    PF_CHECK_LAUNCH("pf_cfg_inpaint_step_pair");
-    return PF_OK;
+    PF_REQUIRE(known && noise && mask, "pf_cfg_inpaint_step_pair: bad arguments (known, noise and mask are required)");
+    return cfg_step_pair("pf_cfg_inpaint_step_pair", x, eu, ec, g, sa, sb, sap, sbp, rows, W, roll, out, out2, tstep, n_tstep,
+                         t_next, x0_prev, k, x0_out, known, noise, mask, ka, kb, known_roll, nullptr, 0, 1, 0.f, nullptr, stream);
 }
 
 extern "C" pf_status pf_cfg_moments(const float* eu, const float* ec, float g, int n_samples, long sample_elems, double* partials,
@@ -1740,51 +1649,17 @@ extern "C" pf_status pf_cfg_rescaled_step_pair(const float* x, const float* eu, 
                                                float* x0_out, const float* known, const float* noise, const float* mask,
                                                float ka, float kb, int known_roll, const double* partials, int n_partials,
                                                long sample_rows, float phi, float* factor_out, void* stream) {
-    PF_REQUIRE(x && eu && ec && out && rows > 0 && W > 0, "pf_cfg_rescaled_step_pair: bad arguments");
-    const bool blend = known || noise || mask;
-    PF_REQUIRE(!blend || (known && noise && mask),
-               "pf_cfg_rescaled_step_pair: known, noise and mask are given together or NULL together (NULL: no blend)");
     PF_REQUIRE(partials, "pf_cfg_rescaled_step_pair: partials is required (pf_cfg_moments writes it)");
     PF_REQUIRE(n_partials >= 1 && n_partials <= PF_CFG_MAX_PARTIALS, "pf_cfg_rescaled_step_pair: n_partials=%d must lie in [1, %d]",
                n_partials, PF_CFG_MAX_PARTIALS);
     PF_REQUIRE(sample_rows > 0 && rows % sample_rows == 0, "pf_cfg_rescaled_step_pair: sample_rows=%ld must divide rows=%ld",
                sample_rows, rows);
     PF_REQUIRE(phi >= 0.0f && phi <= 1.0f, "pf_cfg_rescaled_step_pair: phi=%g must lie in [0, 1]", static_cast<double>(phi));
-    PF_REQUIRE(x0_out || !x0_prev, "pf_cfg_rescaled_step_pair: x0_prev requires x0_out (x0_out == NULL is the DDIM form)");
-    const int max_w = x0_out ? 8192 : 16384;
-    PF_REQUIRE(rows < (1L << 31) && W <= max_w,
-               "pf_cfg_rescaled_step_pair: rows=%ld must be < 2^31 and W=%d <= %d (one row per block, %s staged in LDS)", rows, W,
-               max_w, x0_out ? "two rows" : "one row");
     PF_REQUIRE(sample_rows * W >= 2, "pf_cfg_rescaled_step_pair: a sample of sample_rows=%ld x W=%d has fewer than 2 elements",
                sample_rows, W);
-    PF_REQUIRE(out2 != x && out2 != out && out != eu && out != ec, "pf_cfg_rescaled_step_pair: out2 must be a buffer of its own, out must not alias the predictions");
-    PF_REQUIRE(!x0_out || (x0_out != x && x0_out != eu && x0_out != ec && x0_out != out && x0_out != out2),
-               "pf_cfg_rescaled_step_pair: x0_out must not alias x, the predictions, out or out2 (only x0_prev)");
-    PF_REQUIRE(!x0_prev || (x0_prev != out && x0_prev != out2), "pf_cfg_rescaled_step_pair: x0_prev must not alias out / out2");
-    if (blend) {
-        const float* ops_in[3] = {known, noise, mask};
-        for (const float* p : ops_in)
-            PF_REQUIRE(p != out && p != out2 && p != x0_out,
-                       "pf_cfg_rescaled_step_pair: known / noise / mask must not alias out, out2 or x0_out (they are read at an offset)");
-    }
-    PF_REQUIRE(!tstep || n_tstep > 0, "pf_cfg_rescaled_step_pair: n_tstep must be positive with tstep");
-    int r = roll % W;
-    if (r < 0) r += W;
-    int kr = known_roll % W;
-    if (kr < 0) kr += W;
-    const size_t lds = (x0_out ? 2 : 1) * static_cast<size_t>(W) * sizeof(float);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(rows)), dim3(256), lds, as_stream(stream), x, eu, ec, g, sa, sb, sap,
-                           sbp, x0_out ? x0_prev : nullptr, k, known, noise, mask, ka, kb, kr, W, r, out, out2, x0_out,
-                           reinterpret_cast<long long*>(tstep), n_tstep, static_cast<long long>(t_next), partials, n_partials,
-                           static_cast<int>(sample_rows), phi, factor_out);
-    };
-    if (x0_out && blend) launch(k_cfg_rescaled_rows<true, true>);
-    else if (x0_out) launch(k_cfg_rescaled_rows<true, false>);
-    else if (blend) launch(k_cfg_rescaled_rows<false, true>);
-    else launch(k_cfg_rescaled_rows<false, false>);
-    PF_CHECK_LAUNCH("pf_cfg_rescaled_step_pair");
-    return PF_OK;
+    return cfg_step_pair("pf_cfg_rescaled_step_pair", x, eu, ec, g, sa, sb, sap, sbp, rows, W, roll, out, out2, tstep, n_tstep,
+                         t_next, x0_prev, k, x0_out, known, noise, mask, ka, kb, known_roll, partials, n_partials, sample_rows,
+                         phi, factor_out, stream);
 }
 
 extern "C" pf_status pf_noised_start_pair(const float* z, const float* noise, float ka, float kb, long rows, int W, int roll,

@@ -432,21 +432,41 @@ def cfg_ddim_step(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None):
     return out
 
 
-def cfg_ddim_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0):
-    """cfg_ddim_step as the loop's one-launch state update: ``out`` may be ``x`` itself for any roll, ``out2`` receives a second
-    copy (the other half of the CFG pair the next denoiser call reads), ``tstep`` (int64 device tensor) is set to ``t_next``."""
+def _cfg_step_pair(entry, n_args, x, eps_uncond, eps_cond, guidance, coef, roll, out, out2, tstep, t_next, x0_prev=None, k=0.0,
+                   x0_out=None, known=None, noise=None, mask=None, ka=0.0, kb=0.0, known_roll=0, partials=None, phi=0.0,
+                   samples=1, factor_out=None):
+    """The body of the four cfg_*_step_pair wrappers.  The C argument lists of their entry points are prefixes of one another
+    with ``stream`` last: ``entry`` takes the first ``n_args`` of the one list built here.  Returns (out, x0_out)."""
     W = x.shape[-1]
     rows = x.numel() // W
     if out is None:
         out = torch.empty_like(x)
     assert x.is_contiguous() and out.is_contiguous() and (out2 is None or out2.is_contiguous())
+    for t in (x0_out, x0_prev, known, noise, mask):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel())
     assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
+    n_partials = 0
+    if partials is not None:
+        assert partials.dtype == torch.float64 and partials.is_contiguous() and samples > 0
+        assert partials.numel() % (samples * CFG_MOMENT_DOUBLES) == 0
+        n_partials = partials.numel() // (samples * CFG_MOMENT_DOUBLES)
+    assert factor_out is None or (factor_out.dtype == torch.float32 and factor_out.is_contiguous() and factor_out.numel() >= samples)
     sa, sb, sap, sbp = (float(c) for c in coef)
-    check(_lib.lib().pf_cfg_ddim_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
-                                           rows, W, int(roll), _p(out), _p(out2) if out2 is not None else None,
-                                           _p(tstep) if tstep is not None else None, tstep.numel() if tstep is not None else 0,
-                                           int(t_next), _stream()), "pf_cfg_ddim_step_pair")
-    return out
+    # (a samples that does not divide rows reaches the entry point as a sample_rows that does not, and is refused there)
+    sample_rows = rows // samples if rows % samples == 0 else rows + 1
+    args = [_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp, rows, W, int(roll), _p(out), _p(out2),
+            _p(tstep), tstep.numel() if tstep is not None else 0, int(t_next),                      # ..16: pf_cfg_ddim_step_pair
+            _p(x0_prev), float(k), _p(x0_out),                                                      # ..19: pf_cfg_dpmpp_step_pair
+            _p(known), _p(noise), _p(mask), float(ka), float(kb), int(known_roll),                  # ..25: pf_cfg_inpaint_step_pair
+            _p(partials), n_partials, sample_rows, float(phi), _p(factor_out)]                      # ..30: pf_cfg_rescaled_step_pair
+    check(getattr(_lib.lib(), entry)(*args[:n_args], _stream()), entry)
+    return out, x0_out
+
+
+def cfg_ddim_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0):
+    """cfg_ddim_step as the loop's one-launch state update: ``out`` may be ``x`` itself for any roll, ``out2`` receives a second
+    copy (the other half of the CFG pair the next denoiser call reads), ``tstep`` (int64 device tensor) is set to ``t_next``."""
+    return _cfg_step_pair("pf_cfg_ddim_step_pair", 16, x, eps_uncond, eps_cond, guidance, coef, roll, out, out2, tstep, t_next)[0]
 
 
 def cfg_dpmpp_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0,
@@ -454,23 +474,10 @@ def cfg_dpmpp_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=Non
     """cfg_ddim_step_pair with the DPM-Solver++(2M) correction: out = DDIM(x, eps) + k (x0 - x0_prev), and this step's x0 written
     to ``x0_out`` at the rolled position (the next step's history).  ``x0_prev=None``: a first-order step, out bit-identical to
     cfg_ddim_step_pair.  ``x0_out`` may be ``x0_prev`` itself; returns (out, x0_out)."""
-    W = x.shape[-1]
-    rows = x.numel() // W
-    if out is None:
-        out = torch.empty_like(x)
     if x0_out is None:
         x0_out = torch.empty_like(x)
-    assert x.is_contiguous() and out.is_contiguous() and x0_out.is_contiguous() and (out2 is None or out2.is_contiguous())
-    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
-    assert x0_out.dtype == torch.float32 and x0_out.numel() == x.numel()
-    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
-    sa, sb, sap, sbp = (float(c) for c in coef)
-    check(_lib.lib().pf_cfg_dpmpp_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
-                                            rows, W, int(roll), _p(out), _p(out2) if out2 is not None else None,
-                                            _p(tstep) if tstep is not None else None, tstep.numel() if tstep is not None else 0,
-                                            int(t_next), _p(x0_prev) if x0_prev is not None else None, float(k), _p(x0_out),
-                                            _stream()), "pf_cfg_dpmpp_step_pair")
-    return out, x0_out
+    return _cfg_step_pair("pf_cfg_dpmpp_step_pair", 19, x, eps_uncond, eps_cond, guidance, coef, roll, out, out2, tstep, t_next,
+                          x0_prev, k, x0_out)
 
 
 def cfg_inpaint_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=None, out2=None, tstep=None, t_next=0,
@@ -478,24 +485,8 @@ def cfg_inpaint_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=N
     """cfg_ddim_step_pair (``x0_out=None``) or cfg_dpmpp_step_pair (``x0_out`` given) followed by the known-region blend
     v <- m v + (1 - m) (ka known + kb noise) (mask 1 = generate, 0 = keep).  ``known`` / ``noise`` / ``mask``
     (fp32, the shape of x) are read at column (w - known_roll) mod W.  Returns (out, x0_out); x0_out is None in the DDIM form."""
-    W = x.shape[-1]
-    rows = x.numel() // W
-    if out is None:
-        out = torch.empty_like(x)
-    assert x.is_contiguous() and out.is_contiguous() and (out2 is None or out2.is_contiguous())
-    assert x0_out is None or (x0_out.is_contiguous() and x0_out.dtype == torch.float32 and x0_out.numel() == x.numel())
-    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
-    for t in (known, noise, mask):
-        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel())
-    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
-    sa, sb, sap, sbp = (float(c) for c in coef)
-    opt = lambda t: _p(t) if t is not None else None
-    check(_lib.lib().pf_cfg_inpaint_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
-                                              rows, W, int(roll), _p(out), opt(out2), opt(tstep),
-                                              tstep.numel() if tstep is not None else 0, int(t_next), opt(x0_prev), float(k),
-                                              opt(x0_out), opt(known), opt(noise), opt(mask), float(ka), float(kb),
-                                              int(known_roll), _stream()), "pf_cfg_inpaint_step_pair")
-    return out, x0_out
+    return _cfg_step_pair("pf_cfg_inpaint_step_pair", 25, x, eps_uncond, eps_cond, guidance, coef, roll, out, out2, tstep, t_next,
+                          x0_prev, k, x0_out, known, noise, mask, ka, kb, known_roll)
 
 
 CFG_MOMENT_DOUBLES = 4       # PF_CFG_MOMENT_DOUBLES: (sum c, sum c^2, sum e, sum e^2) per record
@@ -528,33 +519,8 @@ def cfg_rescaled_step_pair(x, eps_uncond, eps_cond, guidance, coef, roll=0, out=
     sample from ``partials`` (cfg_moments' output for the same predictions and guidance; x holds ``samples`` samples of equal
     size).  ``known`` / ``noise`` / ``mask`` all None: no blend (cfg_ddim_step_pair, or cfg_dpmpp_step_pair with ``x0_out``).
     ``factor_out`` (fp32, ``samples`` elements, or None) receives f.  Returns (out, x0_out)."""
-    W = x.shape[-1]
-    rows = x.numel() // W
-    if out is None:
-        out = torch.empty_like(x)
-    assert x.is_contiguous() and out.is_contiguous() and (out2 is None or out2.is_contiguous())
-    assert x0_out is None or (x0_out.is_contiguous() and x0_out.dtype == torch.float32 and x0_out.numel() == x.numel())
-    assert x0_prev is None or (x0_prev.is_contiguous() and x0_prev.dtype == torch.float32 and x0_prev.numel() == x.numel())
-    for t in (known, noise, mask):
-        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == x.numel())
-    assert tstep is None or (tstep.dtype == torch.int64 and tstep.is_contiguous())
-    n_partials = 0
-    if partials is not None:
-        assert partials.dtype == torch.float64 and partials.is_contiguous() and samples > 0
-        assert partials.numel() % (samples * CFG_MOMENT_DOUBLES) == 0
-        n_partials = partials.numel() // (samples * CFG_MOMENT_DOUBLES)
-    assert factor_out is None or (factor_out.dtype == torch.float32 and factor_out.is_contiguous() and factor_out.numel() >= samples)
-    sa, sb, sap, sbp = (float(c) for c in coef)
-    opt = lambda t: _p(t) if t is not None else None
-    # (a samples that does not divide rows reaches the entry point as a sample_rows that does not, and is refused there)
-    sample_rows = rows // samples if rows % samples == 0 else rows + 1
-    check(_lib.lib().pf_cfg_rescaled_step_pair(_p(x), _p(eps_uncond), _p(eps_cond), float(guidance), sa, sb, sap, sbp,
-                                               rows, W, int(roll), _p(out), opt(out2), opt(tstep),
-                                               tstep.numel() if tstep is not None else 0, int(t_next), opt(x0_prev), float(k),
-                                               opt(x0_out), opt(known), opt(noise), opt(mask), float(ka), float(kb),
-                                               int(known_roll), opt(partials), n_partials, sample_rows, float(phi),
-                                               opt(factor_out), _stream()), "pf_cfg_rescaled_step_pair")
-    return out, x0_out
+    return _cfg_step_pair("pf_cfg_rescaled_step_pair", 30, x, eps_uncond, eps_cond, guidance, coef, roll, out, out2, tstep,
+                          t_next, x0_prev, k, x0_out, known, noise, mask, ka, kb, known_roll, partials, phi, samples, factor_out)
 
 
 def noised_start_pair(z, noise, ka, kb, roll=0, *, out, out2=None, tstep=None, t0=0):

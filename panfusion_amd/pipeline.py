@@ -564,16 +564,7 @@ class DenoiseLoop:
         # halves of the CFG pair; panorama -- update + roll for the next iteration (a block owns whole rows, so in place for any
         # roll), both halves, and the next call's timestep words.
         t_next = t if last else self.timesteps[self.i + 1]
-        if self.rescale > 0:
-            self._rescaled_update(eps, pano_eps, coef, last, t_next)
-        elif self.known is not None:
-            self._known_update(eps, pano_eps, coef, last, t_next)
-        elif self.solver is None:
-            ops.cfg_ddim_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:])
-            ops.cfg_ddim_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
-                                   out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next)
-        else:
-            self._dpmpp_update(eps, pano_eps, last, t_next)
+        self._update(eps, pano_eps, coef, last, t_next)
         self._tstep_value = t_next
         self.i += 1
         if not last:
@@ -581,62 +572,38 @@ class DenoiseLoop:
             self.total_rot += self.rot_diff
             self._rot_of.setdefault(tuple(float(v) for v in self.cameras["theta"].reshape(-1)), self.total_rot)
 
-    def _dpmpp_update(self, eps, pano_eps, last, t_next):
-        """The same two launches with the 2M correction; each writes its latent's x0 history (the panorama's rolled like the state)."""
-        coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
-        second = order == 2
-        ops.cfg_dpmpp_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
-                                x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat)
-        ops.cfg_dpmpp_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
-                                out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
-                                x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano)
-
-    def _known_update(self, eps, pano_eps, coef, last, t_next):
-        """The same two launches with the known-region blend after the DDIM or 2M update: x <- m x + (1 - m) r,
-        r = add_noise(known, noise, t_next) = ka known + kb noise, known itself at the last step.  On this grid t_next is the DDIM
-        target of the step, so (ka, kb) are the step's own (sqrt_a_prev, sqrt_1m_a_prev).  The panorama's operands are read at
-        the offset its state has been rolled by before this update: (i + 1) shifts, i counting EXECUTED steps (not total_rot, see
-        result())."""
-        ka, kb = (1.0, 0.0) if last else coef[2:]
-        o = (self.i + 1) * self.shift % self.W
-        blend = lambda z, n, m, roll: dict(known=z, noise=n, mask=m, ka=ka, kb=kb, known_roll=roll)
-        x0 = dict(lat={}, pano={})
+    def _update(self, eps, pano_eps, coef, last, t_next):
+        """The two launches of step() in every mode; each feature adds its keywords once, per latent.
+        A solver: the 2M correction, each launch writes its latent's x0 history (the panorama's rolled like the state).
+        Known content: the blend after the DDIM or 2M update, x <- m x + (1 - m) r, r = add_noise(known, noise,
+        t_next) = ka known + kb noise, known itself at the last step.  On this grid t_next is the DDIM target of the step, so
+        (ka, kb) are the step's own (sqrt_a_prev, sqrt_1m_a_prev).  The panorama's operands are read at the offset its state has
+        been rolled by before this update: (i + 1) shifts, i counting EXECUTED steps (not total_rot, see result()).
+        guidance_rescale > 0: per latent one more launch before the update, for the moments of eps_cond and of
+        the guided prediction; the update runs on f eps_cfg and f stays on the device (rescale_factors: views, panorama)."""
+        lat, pano = {}, {}
+        op = ops.cfg_ddim_step_pair
         if self.solver is not None:
+            op = ops.cfg_dpmpp_step_pair
             coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
-            second = order == 2
-            x0 = dict(lat=dict(x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat),
-                      pano=dict(x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano))
-        ops.cfg_inpaint_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
-                                  **x0["lat"], **blend(self.known_lat, self.noise_lat, self.mask_lat, 0))
-        ops.cfg_inpaint_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
-                                  out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
-                                  **x0["pano"], **blend(self.known_pano, self.noise_pano, self.mask_pano, o))
-
-    def _rescaled_update(self, eps, pano_eps, coef, last, t_next):
-        """guidance_rescale > 0, every form of the update: per latent one launch for the moments of eps_cond and
-        of the guided prediction and one for the update on f eps_cfg -- DDIM or 2M, with the known-region blend of
-        _known_update where the loop has known content.  f stays on the device (rescale_factors: views, panorama)."""
-        x0 = dict(lat={}, pano={})
-        if self.solver is not None:
-            coef, k, order = self.solver.step_coefficients(self.i0 + self.i, first=self.i == 0)
-            second = order == 2
-            x0 = dict(lat=dict(x0_prev=self.x0_lat if second else None, k=k, x0_out=self.x0_lat),
-                      pano=dict(x0_prev=self.x0_pano if second else None, k=k, x0_out=self.x0_pano))
-        blend = dict(lat={}, pano={})
+            lat.update(x0_prev=self.x0_lat if order == 2 else None, k=k, x0_out=self.x0_lat)
+            pano.update(x0_prev=self.x0_pano if order == 2 else None, k=k, x0_out=self.x0_pano)
         if self.known is not None:
+            op = ops.cfg_inpaint_step_pair
             ka, kb = (1.0, 0.0) if last else coef[2:]
             o = (self.i + 1) * self.shift % self.W
-            blend = dict(lat=dict(known=self.known_lat, noise=self.noise_lat, mask=self.mask_lat, ka=ka, kb=kb, known_roll=0),
-                         pano=dict(known=self.known_pano, noise=self.noise_pano, mask=self.mask_pano, ka=ka, kb=kb, known_roll=o))
-        ops.cfg_moments(eps[0], eps[1], self.guidance, samples=1, out=self._moments_lat)
-        ops.cfg_rescaled_step_pair(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:],
-                                   partials=self._moments_lat, phi=self.rescale, factor_out=self.rescale_factors[:1],
-                                   **x0["lat"], **blend["lat"])
-        ops.cfg_moments(pano_eps[0], pano_eps[1], self.guidance, samples=1, out=self._moments_pano)
-        ops.cfg_rescaled_step_pair(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift,
-                                   out=self.pano, out2=self.pano2[1:], tstep=self.tstep, t_next=t_next,
-                                   partials=self._moments_pano, phi=self.rescale, factor_out=self.rescale_factors[1:],
-                                   **x0["pano"], **blend["pano"])
+            lat.update(known=self.known_lat, noise=self.noise_lat, mask=self.mask_lat, ka=ka, kb=kb, known_roll=0)
+            pano.update(known=self.known_pano, noise=self.noise_pano, mask=self.mask_pano, ka=ka, kb=kb, known_roll=o)
+        if self.rescale > 0:
+            op = ops.cfg_rescaled_step_pair
+            lat.update(partials=self._moments_lat, phi=self.rescale, factor_out=self.rescale_factors[:1])
+            pano.update(partials=self._moments_pano, phi=self.rescale, factor_out=self.rescale_factors[1:])
+            ops.cfg_moments(eps[0], eps[1], self.guidance, samples=1, out=self._moments_lat)
+        op(self.lat, eps[0], eps[1], self.guidance, coef, 0, out=self.lat, out2=self.lat2[1:], **lat)
+        if self.rescale > 0:
+            ops.cfg_moments(pano_eps[0], pano_eps[1], self.guidance, samples=1, out=self._moments_pano)
+        op(self.pano, pano_eps[0], pano_eps[1], self.guidance, coef, 0 if last else self.shift, out=self.pano, out2=self.pano2[1:],
+           tstep=self.tstep, t_next=t_next, **pano)
 
     def run(self):
         while self.i < len(self.timesteps):

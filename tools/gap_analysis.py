@@ -11,8 +11,8 @@ def main(path):
     for r in csv.DictReader(open(path)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", r.get("Stream_Id", "0"))))
     rows.sort()
-    # the timed region: the longest stretch of k_cfg_ddim kernels (2 per step) -- take the span of the last 16 of them
-    ddim = [i for i, r in enumerate(rows) if "k_cfg_ddim" in r[2]]
+    # the timed region: the longest stretch of k_cfg_step_rows kernels (2 per step) -- take the span of the last 16 of them
+    ddim = [i for i, r in enumerate(rows) if "k_cfg_step_rows" in r[2]]
     if len(ddim) < 18:
         print("not enough steps in the trace")
         return

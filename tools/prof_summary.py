@@ -54,13 +54,14 @@ def trace(path, out, passes):
 
 def trace_steady(path, out, steps, warmup):
     """Per-kernel table of the TIMED steps only (the whole-run table mixes in weight packing, table building
-    and warm-up).  The loop ends every step with two k_cfg_ddim_rows launches (views, panorama): the window runs from the end of
-    the last warm-up step's second one to the end of the last timed step's -- exactly `steps` steps, nothing else."""
+    and warm-up).  The loop ends every step with two k_cfg_step_rows launches (views, panorama; every sampler and mode): the
+    window runs from the end of the last warm-up step's second one to the end of the last timed step's -- exactly `steps` steps,
+    nothing else."""
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
-    ddim = [i for i, r in enumerate(rows) if "k_cfg_ddim" in r["Kernel_Name"]]
+    ddim = [i for i, r in enumerate(rows) if "k_cfg_step_rows" in r["Kernel_Name"]]
     need = 2 * (warmup + steps)
     if len(ddim) < need:
-        raise SystemExit("trace_steady: %d DDIM launches in the trace, %d expected" % (len(ddim), need))
+        raise SystemExit("trace_steady: %d update launches in the trace, %d expected" % (len(ddim), need))
     lo = ddim[2 * warmup - 1] + 1 if warmup else 0
     hi = ddim[need - 1] + 1
     if not warmup:      # no warm-up step: start at the first kernel after the set-up (the first step's first launch is unknown): refuse
