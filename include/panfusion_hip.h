@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 typedef enum { PF_OK = 0, PF_ERR_ARG = 1, PF_ERR_LAUNCH = 2, PF_ERR_UNSUPPORTED = 3 } pf_status;
-typedef enum { PF_BF16 = 0, PF_F16 = 1, PF_F32 = 2, PF_U8 = 3 } pf_dtype;
+typedef enum { PF_BF16 = 0, PF_F16 = 1, PF_F32 = 2, PF_U8 = 3, PF_F64 = 4 } pf_dtype;
 
 int pf_version(void);
 const char* pf_last_error_string(void);
@@ -66,6 +66,29 @@ pf_status pf_py360_e2p(const void* img, int dtype, int H, int W, int C, const do
                        const double* host_vfov, const double* host_u, const double* host_v,
                        const double* host_in_rot, int ncam, int oh, int ow, int order, void* out,
                        void* stream);
+
+/* Cube maps, external/py360convert/e2c.py:6-40 (called from utils/pano.py:146-147 Equirectangular.to_cubemap): `n`
+ * equirectangular images img [n][H][W][C] (PF_U8 or PF_F32, channels last) -> out [n][face_w][6 face_w][C], same
+ * dtype: the reference's 'horizon' layout, faces F R B L U D side by side.  Rays are utils.py:5-37 xyzcube (float32
+ * linspace(-0.5, 0.5, face_w) in-face coordinates); utils.py:82-114 xyz2uv / uv2coor are evaluated in double from
+ * those float32 values (the reference evaluates them in float32; DESIGN.md 4.2 bounds the difference).  order 0 =
+ * nearest, 1 = bilinear; the sampler is pf_py360_e2p's (pole rows, legacy 'wrap', scipy's uint8 store). */
+pf_status pf_py360_e2c(const void* img, int dtype, int n, int H, int W, int C, int face_w, int order,
+                       void* out, void* stream);
+
+/* external/py360convert/c2e.py:6-64 (called from utils/pano.py:124-125 Cubemap.to_equirectangular; scripts/
+ * stitch_mp3d.py makes every Matterport3D panorama with it): `n` cube maps cube [n][face_w][6 face_w][C] in horizon
+ * layout (PF_U8 or PF_F32) -> out [n][h][w][C], w % 8 == 0.  out_dtype PF_F64 is what the reference returns for any
+ * input dtype; PF_F32 / PF_U8 are numpy's astype of that result (PF_U8 truncates, as Equirectangular.save does).
+ * host_ceil_rows: w / 4 host ints, the per-column U / D boundary rows of utils.py:47-64 equirect_facetype
+ * (h // 2 - round(arctan(cos(linspace(-pi, pi, w // 4) / 4)) * h / pi)), computed by the caller with numpy so that
+ * a rounding tie falls as in the reference; each must lie in [0, h].  In-face coordinates: c2e.py:40-57 in double
+ * from the float32 utils.py:40-44 equirect_uvgrid values.  Sampling: utils.py:135-173 sample_cubefaces (faces R, B
+ * flipped left-right, U up-down; two rows then two columns appended from the neighbouring faces; map_coordinates
+ * mode='wrap', order 0 / 1) folded into addressing of the unpadded input; the zero-weight tap on the face axis is
+ * not read. */
+pf_status pf_py360_c2e(const void* cube, int dtype, int n, int face_w, int C, const int* host_ceil_rows,
+                       int h, int w, int order, int out_dtype, void* out, void* stream);
 
 /* Integer gather indices of kornia.remap(mode='nearest', align_corners=True) -> F.grid_sample
  * (e2p.py:76): idx[i] = iy*src_w+ix or -1 when the sample falls outside.  n entries. */

@@ -560,6 +560,41 @@ template <> __device__ __forceinline__ uint8_t p360_store<uint8_t>(double t) {  
     return static_cast<uint8_t>(t);
 }
 
+// utils.py:125-132 sample_equirec at one position (cx, cy), all C channels of one image -> dst[0 .. C)
+template <typename E>
+__device__ __forceinline__ void p360_sample_equirec(const E* __restrict__ img, int H, int W, int C, double cx, double cy,
+                                                    int order, E* __restrict__ dst) {
+    const long HP = H + 2;                                  // rows H, H+1: last / first row rolled by W/2
+    const double y = scipy_wrap_coord(cy, HP), x = scipy_wrap_coord(cx, W);
+    auto pixel = [&](long iy, long ix, int c) -> double {
+        iy = scipy_wrap_index(iy, HP);
+        ix = scipy_wrap_index(ix, W);
+        if (iy >= H) {                                      // np.roll(row, W // 2): padded[j] = row[(j - W/2) mod W]
+            long src = (ix - W / 2) % W;
+            if (src < 0) src += W;
+            ix = src;
+            iy = iy == H ? H - 1 : 0;
+        }
+        return static_cast<double>(img[(iy * W + ix) * C + c]);
+    };
+    if (order == 0) {
+        const long iy = static_cast<long>(floor(y + 0.5)), ix = static_cast<long>(floor(x + 0.5));
+        for (int c = 0; c < C; ++c) dst[c] = p360_store<E>(pixel(iy, ix, c));
+    } else {
+        const double fy0 = floor(y), fx0 = floor(x);
+        const long y0 = static_cast<long>(fy0), x0 = static_cast<long>(fx0);
+        const double wy1 = y - fy0, wx1 = x - fx0, wy0 = 1.0 - wy1, wx0 = 1.0 - wx1;
+        for (int c = 0; c < C; ++c) {
+            double acc = 0.0;
+            acc = acc + pixel(y0, x0, c) * wy0 * wx0;
+            acc = acc + pixel(y0, x0 + 1, c) * wy0 * wx1;
+            acc = acc + pixel(y0 + 1, x0, c) * wy1 * wx0;
+            acc = acc + pixel(y0 + 1, x0 + 1, c) * wy1 * wx1;
+            dst[c] = p360_store<E>(acc);
+        }
+    }
+}
+
 template <typename E>
 __global__ void k_py360_e2p(const P360Batch cams, int ncam, const E* __restrict__ img, int H, int W, int C,
                             int oh, int ow, int order, E* __restrict__ out) {
@@ -583,36 +618,7 @@ __global__ void k_py360_e2p(const P360Batch cams, int ncam, const E* __restrict_
     const double lat = atan2(v[1], sqrt(v[0] * v[0] + v[2] * v[2]));
     const double cx = (lon / (2 * kPi) + 0.5) * W - 0.5;
     const double cy = (-lat / kPi + 0.5) * H - 0.5;
-    const long HP = H + 2;                                  // rows H, H+1: last / first row rolled by W/2
-    const double y = scipy_wrap_coord(cy, HP), x = scipy_wrap_coord(cx, W);
-    auto pixel = [&](long iy, long ix, int c) -> double {
-        iy = scipy_wrap_index(iy, HP);
-        ix = scipy_wrap_index(ix, W);
-        if (iy >= H) {                                      // np.roll(row, W // 2): padded[j] = row[(j - W/2) mod W]
-            long src = (ix - W / 2) % W;
-            if (src < 0) src += W;
-            ix = src;
-            iy = iy == H ? H - 1 : 0;
-        }
-        return static_cast<double>(img[(iy * W + ix) * C + c]);
-    };
-    E* dst = out + i * C;
-    if (order == 0) {
-        const long iy = static_cast<long>(floor(y + 0.5)), ix = static_cast<long>(floor(x + 0.5));
-        for (int c = 0; c < C; ++c) dst[c] = p360_store<E>(pixel(iy, ix, c));
-    } else {
-        const double fy0 = floor(y), fx0 = floor(x);
-        const long y0 = static_cast<long>(fy0), x0 = static_cast<long>(fx0);
-        const double wy1 = y - fy0, wx1 = x - fx0, wy0 = 1.0 - wy1, wx0 = 1.0 - wx1;
-        for (int c = 0; c < C; ++c) {
-            double acc = 0.0;
-            acc = acc + pixel(y0, x0, c) * wy0 * wx0;
-            acc = acc + pixel(y0, x0 + 1, c) * wy0 * wx1;
-            acc = acc + pixel(y0 + 1, x0, c) * wy1 * wx0;
-            acc = acc + pixel(y0 + 1, x0 + 1, c) * wy1 * wx1;
-            dst[c] = p360_store<E>(acc);
-        }
-    }
+    p360_sample_equirec<E>(img, H, W, C, cx, cy, order, out + i * C);
 }
 
 // utils.py:231-243 rotation_matrix(rad, ax), same operation order, double
@@ -666,6 +672,213 @@ extern "C" pf_status pf_py360_e2p(const void* img, int dtype, int H, int W, int 
                                ow, order, static_cast<uint8_t*>(out) + c0 * per * C);
     }
     PF_CHECK_LAUNCH("pf_py360_e2p");
+    return PF_OK;
+}
+
+// ---- py360convert.e2c / c2e (cube maps, horizon layout [face_w][6 face_w][C], faces F R B L U D) ------------
+// external/py360convert/e2c.py:6-40 + utils.py:5-37 xyzcube: the ray of pixel (r, c) of face f has the in-face
+// coordinates (rng[c], -rng[r]), rng = float32 linspace(-0.5, 0.5, face_w), and +-0.5 on the face's own axis;
+// xyz2uv / uv2coor (utils.py:82-91,104-114) run in float32 in the reference and in double here, from the same
+// float32 inputs (numpy's float32 atan2 is not correctly rounded and differs between builds: DESIGN.md 4.2);
+// the sample is utils.py:125-132, shared with k_py360_e2p.
+template <typename E>
+__global__ void k_py360_e2c(const E* __restrict__ img, int n, int H, int W, int C, int fw, int order,
+                            E* __restrict__ out) {
+    const long i = blockIdx.x * static_cast<long>(blockDim.x) + threadIdx.x;
+    const long per = static_cast<long>(fw) * 6 * fw;
+    if (i >= n * per) return;
+    const int col = i % (6 * fw), r = (i / (6 * fw)) % fw, b = i / per;
+    const int f = col / fw, c = col % fw;
+    const double gx = static_cast<double>(static_cast<float>(linspace_at(-0.5, 0.5, fw, c)));
+    const double gy = -static_cast<double>(static_cast<float>(linspace_at(-0.5, 0.5, fw, r)));
+    double x, y, z;
+    switch (f) {
+        case 0: x = gx; y = gy; z = 0.5; break;             // F
+        case 1: z = gx; y = gy; x = 0.5; break;             // R
+        case 2: x = gx; y = gy; z = -0.5; break;            // B
+        case 3: z = gx; y = gy; x = -0.5; break;            // L
+        case 4: x = gx; z = gy; y = 0.5; break;             // U
+        default: x = gx; z = gy; y = -0.5; break;           // D
+    }
+    const double lon = atan2(x, z);
+    const double lat = atan2(y, sqrt(x * x + z * z));
+    const double cx = (lon / (2 * kPi) + 0.5) * W - 0.5;
+    const double cy = (-lat / kPi + 0.5) * H - 0.5;
+    p360_sample_equirec<E>(img + static_cast<long>(b) * H * W * C, H, W, C, cx, cy, order, out + i * C);
+}
+
+extern "C" pf_status pf_py360_e2c(const void* img, int dtype, int n, int H, int W, int C, int face_w, int order,
+                                  void* out, void* stream) {
+    PF_REQUIRE(img && out, "pf_py360_e2c: null pointer");
+    PF_REQUIRE(n > 0 && H > 1 && W > 1 && C > 0, "pf_py360_e2c: bad sizes");
+    PF_REQUIRE(face_w > 1, "pf_py360_e2c: face_w must be at least 2");
+    PF_REQUIRE(order == 0 || order == 1, "pf_py360_e2c: order must be 0 (nearest) or 1 (bilinear)");
+    PF_REQUIRE(dtype == PF_F32 || dtype == PF_U8, "pf_py360_e2c: dtype must be PF_F32 or PF_U8");
+    const dim3 grid(cdiv(static_cast<long>(n) * face_w * 6 * face_w, 256)), block(256);
+    if (dtype == PF_F32)
+        hipLaunchKernelGGL(k_py360_e2c<float>, grid, block, 0, as_stream(stream), static_cast<const float*>(img), n, H, W, C,
+                           face_w, order, static_cast<float*>(out));
+    else
+        hipLaunchKernelGGL(k_py360_e2c<uint8_t>, grid, block, 0, as_stream(stream), static_cast<const uint8_t*>(img), n, H, W,
+                           C, face_w, order, static_cast<uint8_t*>(out));
+    PF_CHECK_LAUNCH("pf_py360_e2c");
+    return PF_OK;
+}
+
+// external/py360convert/c2e.py:6-64.  utils.py:135-173 sample_cubefaces flips faces R, B left-right and U up-down,
+// appends two rows after row face_w - 1 of every face, then two columns after column face_w - 1 (of the row-extended
+// faces), and samples [6][face_w + 2][face_w + 2] by map_coordinates(mode='wrap').  c2e_row_ext / c2e_source fold
+// that construction into an address of the unpadded input: (f, r, c) of the padded array -> (f, r, c) of the
+// flipped faces G (utils.py:137-139), false where the reference's pad keeps its initial zero.
+__device__ __forceinline__ void c2e_row_ext(int& f, int& r, int& c, int F) {     // utils.py:142-155, c < F
+    if (r < F) return;
+    const int m = F - 1;
+    switch (2 * f + (r - F)) {
+        case 0: f = 5; r = 0; break;                        // pad_ud[0, 0] = G[5, 0, :]
+        case 1: f = 4; r = m; break;                        // pad_ud[0, 1] = G[4, -1, :]
+        case 2: f = 5; r = c; c = m; break;                 // pad_ud[1, 0] = G[5, :, -1]
+        case 3: f = 4; r = m - c; c = m; break;             // pad_ud[1, 1] = G[4, ::-1, -1]
+        case 4: f = 5; r = m; c = m - c; break;             // pad_ud[2, 0] = G[5, -1, ::-1]
+        case 5: f = 4; r = 0; c = m - c; break;             // pad_ud[2, 1] = G[4, 0, ::-1]
+        case 6: f = 5; r = m - c; c = 0; break;             // pad_ud[3, 0] = G[5, ::-1, 0]
+        case 7: f = 4; r = c; c = 0; break;                 // pad_ud[3, 1] = G[4, :, 0]
+        case 8: f = 0; r = 0; break;                        // pad_ud[4, 0] = G[0, 0, :]
+        case 9: f = 2; r = 0; c = m - c; break;             // pad_ud[4, 1] = G[2, 0, ::-1]
+        case 10: f = 2; r = m; c = m - c; break;            // pad_ud[5, 0] = G[2, -1, ::-1]
+        default: f = 0; r = m; break;                       // pad_ud[5, 1] = G[0, -1, :]
+    }
+}
+__device__ __forceinline__ bool c2e_source(int& f, int& r, int& c, int F) {      // r, c in [0, F + 2)
+    if (c >= F) {                                           // utils.py:158-171 on the row-extended faces
+        const int k = c - F;
+        if (f < 4) {                                        // pad_lr[f, :, 0] = E[f + 1, :, 0], [f, :, 1] = E[f - 1, :, -1]
+            f = (f + (k == 0 ? 1 : 3)) & 3;
+            c = k == 0 ? 0 : F - 1;
+        } else {
+            if (r < 1 || r > F) return false;               // pad_lr[4 / 5, 1:-1, k]: rows 0 and F + 1 stay zero
+            const int j = r - 1;
+            if (f == 4) {                                   // E[1, 0, ::-1] | E[3, 0, :]
+                f = k == 0 ? 1 : 3;
+                c = k == 0 ? F - 1 - j : j;
+                r = 0;
+            } else {                                        // E[1, -2, :] | E[3, -2, ::-1]: row -2 of F + 2 rows is pad row F
+                f = k == 0 ? 1 : 3;
+                c = k == 0 ? j : F - 1 - j;
+                r = F;
+            }
+        }
+    }
+    c2e_row_ext(f, r, c, F);
+    return true;
+}
+
+template <typename O> __device__ __forceinline__ O c2e_store(double t);          // numpy's astype of the float64 result
+template <> __device__ __forceinline__ double c2e_store<double>(double t) { return t; }
+template <> __device__ __forceinline__ float c2e_store<float>(double t) { return static_cast<float>(t); }
+template <> __device__ __forceinline__ uint8_t c2e_store<uint8_t>(double t) {
+    return static_cast<uint8_t>(static_cast<long long>(t));                      // truncates (Equirectangular.save)
+}
+
+constexpr int C2E_ROWS = 768;                               // quarter-columns per launch (3 KiB of kernel arguments)
+struct C2eRows { int ceil_row[C2E_ROWS]; };
+
+// One thread per output pixel.  equirect_facetype (utils.py:47-64): column x belongs to side face j / (w/4),
+// j = (x - 3w/8) mod w; rows above ceil_row[j mod (w/4)] are U, the mirrored rows D (D wins where both hold).
+template <typename E, typename O>
+__global__ void k_py360_c2e(const C2eRows rows, int q0, int nq, const E* __restrict__ cube, int n, int F, int C, int h,
+                            int w, int order, O* __restrict__ out) {
+    const long i = blockIdx.x * static_cast<long>(blockDim.x) + threadIdx.x;
+    if (i >= static_cast<long>(n) * h * 4 * nq) return;
+    const int qq = i % nq, side = (i / nq) % 4, yo = (i / (4 * nq)) % h, b = i / (static_cast<long>(4) * nq * h);
+    const int xo = (side * (w / 4) + q0 + qq + 3 * w / 8) % w;
+    const int ceil_row = rows.ceil_row[qq];
+    const int tp = yo >= h - ceil_row ? 5 : (yo < ceil_row ? 4 : side);
+    // equirect_uvgrid (utils.py:40-44): float32 linspaces, v halved in float32 (exact)
+    const double u = static_cast<double>(static_cast<float>(linspace_at(-kPi, kPi, w, xo)));
+    const double v = static_cast<double>(static_cast<float>(linspace_at(kPi, -kPi, h, yo))) / 2;
+    double cx, cy;
+    if (tp < 4) {                                           // c2e.py:40-43
+        const double a = u - kPi * tp / 2;
+        cx = 0.5 * tan(a);
+        cy = -0.5 * tan(v) / cos(a);
+    } else if (tp == 4) {                                   // c2e.py:45-48
+        const double c = 0.5 * tan(kPi / 2 - v);
+        cx = c * sin(u);
+        cy = c * cos(u);
+    } else {                                                // c2e.py:50-53
+        const double c = 0.5 * tan(kPi / 2 - fabs(v));
+        cx = c * sin(u);
+        cy = -c * cos(u);
+    }
+    cx = (fmin(fmax(cx, -0.5), 0.5) + 0.5) * F;             // c2e.py:56-57
+    cy = (fmin(fmax(cy, -0.5), 0.5) + 0.5) * F;
+    const long FP = F + 2;
+    const double y = scipy_wrap_coord(cy, FP), x = scipy_wrap_coord(cx, FP);
+    const E* src = cube + static_cast<long>(b) * F * 6 * F * C;
+    auto pixel = [&](long iy, long ix, int ch) -> double {
+        int f = tp, r = static_cast<int>(scipy_wrap_index(iy, FP)), c = static_cast<int>(scipy_wrap_index(ix, FP));
+        if (!c2e_source(f, r, c, F)) return 0.0;
+        if (f == 1 || f == 2) c = F - 1 - c;                // utils.py:137-139
+        if (f == 4) r = F - 1 - r;
+        return static_cast<double>(src[(static_cast<long>(r) * 6 * F + f * F + c) * C + ch]);
+    };
+    O* dst = out + ((static_cast<long>(b) * h + yo) * w + xo) * C;
+    // the face axis: tp is an integer coordinate, its second tap has weight 0 and is not read
+    if (order == 0) {
+        const long iy = static_cast<long>(floor(y + 0.5)), ix = static_cast<long>(floor(x + 0.5));
+        for (int ch = 0; ch < C; ++ch) dst[ch] = c2e_store<O>(pixel(iy, ix, ch));
+    } else {
+        const double fy0 = floor(y), fx0 = floor(x);
+        const long y0 = static_cast<long>(fy0), x0 = static_cast<long>(fx0);
+        const double wy1 = y - fy0, wx1 = x - fx0, wy0 = 1.0 - wy1, wx0 = 1.0 - wx1;
+        for (int ch = 0; ch < C; ++ch) {
+            double acc = 0.0;
+            acc = acc + pixel(y0, x0, ch) * wy0 * wx0;
+            acc = acc + pixel(y0, x0 + 1, ch) * wy0 * wx1;
+            acc = acc + pixel(y0 + 1, x0, ch) * wy1 * wx0;
+            acc = acc + pixel(y0 + 1, x0 + 1, ch) * wy1 * wx1;
+            dst[ch] = c2e_store<O>(acc);
+        }
+    }
+}
+
+template <typename E>
+static void launch_c2e(const C2eRows& rows, int q0, int nq, const void* cube, int n, int F, int C, int h, int w, int order,
+                       int out_dtype, void* out, hipStream_t st) {
+    const dim3 grid(cdiv(static_cast<long>(n) * h * 4 * nq, 256)), block(256);
+    const E* src = static_cast<const E*>(cube);
+    if (out_dtype == PF_F64)
+        hipLaunchKernelGGL((k_py360_c2e<E, double>), grid, block, 0, st, rows, q0, nq, src, n, F, C, h, w, order,
+                           static_cast<double*>(out));
+    else if (out_dtype == PF_F32)
+        hipLaunchKernelGGL((k_py360_c2e<E, float>), grid, block, 0, st, rows, q0, nq, src, n, F, C, h, w, order,
+                           static_cast<float*>(out));
+    else
+        hipLaunchKernelGGL((k_py360_c2e<E, uint8_t>), grid, block, 0, st, rows, q0, nq, src, n, F, C, h, w, order,
+                           static_cast<uint8_t*>(out));
+}
+
+extern "C" pf_status pf_py360_c2e(const void* cube, int dtype, int n, int face_w, int C, const int* host_ceil_rows, int h,
+                                  int w, int order, int out_dtype, void* out, void* stream) {
+    PF_REQUIRE(cube && out && host_ceil_rows, "pf_py360_c2e: null pointer");
+    PF_REQUIRE(n > 0 && C > 0 && h > 1 && w > 1, "pf_py360_c2e: bad sizes");
+    PF_REQUIRE(face_w > 1, "pf_py360_c2e: face_w must be at least 2");
+    PF_REQUIRE(w % 8 == 0, "pf_py360_c2e: w must be a multiple of 8 (equirect_facetype)");
+    PF_REQUIRE(order == 0 || order == 1, "pf_py360_c2e: order must be 0 (nearest) or 1 (bilinear)");
+    PF_REQUIRE(dtype == PF_F32 || dtype == PF_U8, "pf_py360_c2e: dtype must be PF_F32 or PF_U8");
+    PF_REQUIRE(out_dtype == PF_F64 || out_dtype == PF_F32 || out_dtype == PF_U8,
+               "pf_py360_c2e: out_dtype must be PF_F64, PF_F32 or PF_U8");
+    for (int q = 0; q < w / 4; ++q)
+        PF_REQUIRE(host_ceil_rows[q] >= 0 && host_ceil_rows[q] <= h, "pf_py360_c2e: ceil_rows[%d] = %d outside [0, %d]", q,
+                   host_ceil_rows[q], h);
+    for (int q0 = 0; q0 < w / 4; q0 += C2E_ROWS) {          // one launch up to w = 3072
+        const int nq = w / 4 - q0 < C2E_ROWS ? w / 4 - q0 : C2E_ROWS;
+        C2eRows rows;
+        for (int q = 0; q < C2E_ROWS; ++q) rows.ceil_row[q] = q < nq ? host_ceil_rows[q0 + q] : 0;
+        if (dtype == PF_F32) launch_c2e<float>(rows, q0, nq, cube, n, face_w, C, h, w, order, out_dtype, out, as_stream(stream));
+        else launch_c2e<uint8_t>(rows, q0, nq, cube, n, face_w, C, h, w, order, out_dtype, out, as_stream(stream));
+    }
+    PF_CHECK_LAUNCH("pf_py360_c2e");
     return PF_OK;
 }
 

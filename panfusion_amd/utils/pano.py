@@ -1,6 +1,8 @@
 """Panorama helpers on the denoising path (mirror of the reference's
-``utils/pano.py:21-105``): camera samplers (host, radians) and the circular
-width padding."""
+``utils/pano.py:21-171``): camera samplers (host, radians), the circular
+width padding and the dataset's image holders ``Cubemap`` / ``Equirectangular``."""
+import os
+
 import numpy as np
 
 from .. import ops
@@ -50,13 +52,46 @@ def unpad_pano(pano_pad, padding):
     return pano_pad[..., padding:-padding]
 
 
+class Cubemap:
+    """The six-face skybox holder (utils/pano.py:108-139), horizon layout [face_w, 6 face_w, C] in ``.cubemap``;
+    ``to_equirectangular`` runs on the HIP kernel behind ``external.py360convert.c2e``."""
+
+    def __init__(self, cubemap, cube_format):
+        from ..external.py360convert import to_horizon
+        cubemap = to_horizon(cubemap, cube_format)
+        assert len(cubemap.shape) == 3
+        assert cubemap.shape[0] * 6 == cubemap.shape[1]
+        self.cubemap = cubemap
+
+    def to_equirectangular(self, h, w, mode="bilinear"):
+        from ..external.py360convert import c2e
+        return Equirectangular(c2e(self.cubemap, h, w, mode, cube_format="horizon"))
+
+    @classmethod
+    def from_mp3d_skybox(cls, mp3d_skybox_path, scene, view):
+        """utils/pano.py:127-139: Matterport3D stores skybox0..5 as U L F R B D, with R and B mirrored, U mirrored
+        up-down and U, D a quarter turn away from this package's face orientation."""
+        from PIL import Image
+        folder = os.path.join(mp3d_skybox_path, scene, "matterport_skybox_images")
+        faces = {key: np.array(Image.open(os.path.join(folder, "%s_skybox%d_sami.jpg" % (view, i))))
+                 for i, key in enumerate("ULFRBD")}
+        faces["R"], faces["B"] = np.flip(faces["R"], 1), np.flip(faces["B"], 1)
+        faces["U"] = np.rot90(np.flip(faces["U"], 0), 1)
+        faces["D"] = np.rot90(faces["D"], 1)
+        return cls(faces, "dict")
+
+
 class Equirectangular:
     """The dataset's panorama holder (utils/pano.py:142-171), numpy image in ``.equirectangular``; the view crops
     (``to_perspective``, and the batched ``to_perspectives`` the dataset loop wants) run on the HIP kernel behind
-    ``external.py360convert.e2p``."""
+    ``external.py360convert.e2p``, ``to_cubemap`` on the one behind ``e2c``."""
 
     def __init__(self, equirectangular):
         self.equirectangular = equirectangular
+
+    def to_cubemap(self, face_w=256, mode="bilinear"):
+        from ..external.py360convert import e2c
+        return Cubemap(e2c(self.equirectangular, face_w, mode, cube_format="horizon"), "horizon")
 
     def to_perspective(self, fov, yaw, pitch, hw, mode="bilinear"):
         from ..external.py360convert import e2p
