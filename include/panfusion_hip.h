@@ -591,9 +591,33 @@ typedef struct {
                       * by a second launch in a fixed order (no atomics).  NULL: never split. */
 } pf_attn_desc;
 
+/* Layout rules (pf_attention and pf_attention_wide check them in one place; anything else is PF_ERR_ARG before any launch): q, k, vt, out
+ * non-NULL and 16-byte aligned; B, H, nq, nk > 0; q_ld, k_ld multiples of 8, o_ld, vt_ld of 4; q_ld, k_ld and o_ld cover the H * D
+ * columns of a row; vt_ld >= nk rounded up to 32; q_bs, k_bs multiples of 8, vt_bs, o_bs of 4; bias and flags come together (with a
+ * bias: nk % 4 == 0, bias_ld % 4 == 0, bias_ld >= nk, flags_ld >= ceil(nk / 32)); the planned grid is launchable (each dimension within
+ * HIP's limits, workgroups x threads of the 1-D grids under 2^32).  The last two rules refuse only descriptors whose launch would read or
+ * write out of bounds or fail at launch. */
 pf_status pf_attention(const pf_attn_desc* desc, void* stream);
-/* Bytes of pf_attn_desc.workspace that let pf_attention split the key range of this problem (0: it would not split). */
+/* Bytes of pf_attn_desc.workspace that let pf_attention split the key range of this problem (0: it would not split): workspace_bytes
+ * of the plan below; 0 for a bad descriptor. */
 size_t pf_attention_workspace_size(const pf_attn_desc* desc);
+/* The whole plan pf_attention resolves for a problem: everything that selects a kernel instantiation or sizes the grid or the scratch. */
+typedef struct {
+    int kernel;          /* 0 k_attention (no LDS), 1 k_attention_lds, 2 k_attention_pp, 3 k_attention_pp2 */
+    int pipelined;       /* k_attention_lds: its PIPE template argument; 0 for the other kernels */
+    int occupancy;       /* k_attention_lds: its OCC template argument; 0 for the other kernels */
+    int msum;            /* k_attention_lds: its MSUM template argument; 0 for the other kernels */
+    int block_queries;   /* query rows of a workgroup: 128, or 256 for the ping-pong kernels */
+    int threads;         /* 256 or 512 */
+    int splits;          /* key-range splits S of the launch (1: not split); S > 1 adds the k_attention_merge launch */
+    int split_tiles;     /* 64-key tiles per split (even), 0 when splits == 1 */
+    unsigned grid_x, grid_y, grid_z;
+    size_t workspace_bytes;   /* scratch of exactly this plan, 0 when splits == 1 */
+} pf_attn_plan;
+/* Looks only at the scalar members of desc and at whether bias and lse are NULL (nothing is dereferenced, no GPU is needed), validates
+ * nothing else and reports the plan of a launch that hands over the workspace it asks for (a launch without it runs the same plan
+ * unsplit).  PF_ERR_ARG for a NULL pointer, non-positive B, H, nq or nk, or a head dim other than 32 or 64. */
+pf_status pf_attention_plan(const pf_attn_desc* desc, pf_attn_plan* out);
 
 /* Flash attention at WIDE heads (replaces the mid-block Attention(heads=1, dim_head=C) of diffusers' AutoencoderKL --
  * baddbmm + softmax + bmm over an N x N score matrix -- reached from models/pano/PanoGenerator.py:213-238):

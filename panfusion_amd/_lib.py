@@ -60,6 +60,15 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnPlan(C.Structure):
+    """pf_attn_plan"""
+    _fields_ = [
+        ("kernel", c_int), ("pipelined", c_int), ("occupancy", c_int), ("msum", c_int), ("block_queries", c_int), ("threads", c_int),
+        ("splits", c_int), ("split_tiles", c_int), ("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint),
+        ("workspace_bytes", c_size_t),
+    ]
+
+
 class LinearWsDesc(C.Structure):
     """pf_linear_ws_desc"""
     _fields_ = [
@@ -176,6 +185,7 @@ SIGNATURES = {
                                c_void_p, c_void_p]),
     "pf_attention": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "pf_attention_workspace_size": (c_size_t, [C.POINTER(AttnDesc)]),
+    "pf_attention_plan": (c_int, [C.POINTER(AttnDesc), C.POINTER(AttnPlan)]),
     "pf_attention_wide": (c_int, [C.POINTER(AttnDesc), c_void_p]),
     "pf_attention_delta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_long, c_void_p, c_void_p]),
     "pf_attention_bwd": (c_int, [C.POINTER(AttnBwdDesc), c_void_p]),

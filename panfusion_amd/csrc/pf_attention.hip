@@ -18,7 +18,7 @@
 // Replaces xformers.ops.memory_efficient_attention (models/modules/transformer.py:57-74) and the
 // diffusers AttnProcessor (baddbmm + softmax + bmm) inside unet.*.attentions[j]
 // (models/pano/MVGenModel.py:104,116,185,190,227,241).
-#include "pf_common.h"
+#include "pf_attention_plan.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
@@ -1349,156 +1349,98 @@ __global__ __launch_bounds__(512, 1) void k_attention_pp2(const AttnParams p) {
     }
 }
 
-static bool use_lds_attention() {
-    static int v = -1;                     // PF_ATTENTION_IMPL=direct selects the no-LDS kernel (A/B switch)
-    if (v < 0) { const char* e = getenv("PF_ATTENTION_IMPL"); v = (e && e[0] == 'd') ? 0 : 1; }
-    return v == 1;
+// What the planner (pf_attention_plan.hip) has to know about how THIS file was built: it follows the kernels it is linked with.
+extern const bool attn_build_bufload = PF_ATTN_BUFLOAD != 0;
+#ifdef PF_ATTN_PP_TIMING
+extern const bool attn_build_pp_timing = true;
+#else
+extern const bool attn_build_pp_timing = false;
+#endif
+
+// The k_attention_lds instantiation a plan names, as (D, bias, PIPE, OCC, MSUM): these eleven are the ones that exist.  false: none
+// of them (a planner bug, reported by the caller).
+template <typename T>
+static bool launch_lds(const pf_attn_plan& g, int D, bool bias, const AttnParams& p, hipStream_t st) {
+    const dim3 grid(g.grid_x, g.grid_y, g.grid_z), block(g.threads);
+#define PF_LDS(D_, BIAS_, PIPE_, OCC_, MSUM_)                                                                  \
+    if (D == D_ && bias == BIAS_ && g.pipelined == PIPE_ && g.occupancy == OCC_ && g.msum == MSUM_) {          \
+        hipLaunchKernelGGL((k_attention_lds<T, D_, BIAS_, PIPE_, OCC_, MSUM_>), grid, block, 0, st, p);        \
+        return true;                                                                                           \
+    }
+    PF_LDS(64, true, true, 2, false)
+    PF_LDS(64, false, true, 2, false)
+    PF_LDS(64, false, false, 3, true)
+    PF_LDS(64, false, false, 3, false)
+    PF_LDS(32, true, false, 4, false)
+    PF_LDS(32, true, false, 5, false)
+    PF_LDS(32, true, true, 3, true)
+    PF_LDS(32, true, true, 3, false)
+    PF_LDS(32, false, false, 4, false)
+    PF_LDS(32, false, false, 5, false)
+    PF_LDS(32, false, true, 3, false)
+#undef PF_LDS
+    return false;
 }
 
-// A/B switches.  PF_ATTENTION_OCC (D = 64): 3 = one score array, three waves per SIMD (default), 2 = register-pipelined
-// scores, two waves per SIMD.  PF_ATTENTION_OCC32 (D = 32): 4 (default since round 6: 122 registers, no scratch; -0.2 ... -0.35 ms per step on three boxes,
-// profiles/r6o_ab_epa_occupancy.txt) | 5 = not pipelined at that occupancy, 3 = register-pipelined scores at three waves per SIMD (rounds 3-5).
-static int attention_occupancy(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-// Split of the key range (round 6): a launch of the biased D = 32 kernel (EPA) whose query blocks fill less than ~0.95 of the chip's workgroup slots
-// (256 CUs x 4) with a long key walk is cut into S splits of an even number of key tiles, at least MIN_TILES each, aiming at ~1.9 rounds of
-// workgroups.  PF_ATTENTION_SPLIT=0 disables it (read per call: the tests run both).
-struct AttnSplit { int S, tiles; size_t o_bytes, bytes; };
-static AttnSplit attention_split(const pf_attn_desc* d) {
-    AttnSplit r{1, 0, 0, 0};
-    if (!attention_occupancy("PF_ATTENTION_SPLIT", 1) || d->D != 32 || !d->bias || d->lse || d->o_ld % 8 != 0 || d->o_bs % 8 != 0) return r;
-    static const int occ32 = attention_occupancy("PF_ATTENTION_OCC32", 4), min_tiles = attention_occupancy("PF_ATTENTION_SPLIT_MIN_TILES", 8);
-    if (occ32 != 4 && occ32 != 5) return r;                                   // (the register-pipelined form walks three LDS buffers: never split)
-    const long blocks = cdiv(d->nq, 128) * d->H * d->B, slots = 256L * occ32;
-    const int nkt = (d->nk + 63) / 64;
-    if (blocks * 20 >= slots * 19) return r;
-    int S = static_cast<int>((slots * 19 / 10 + blocks / 2) / blocks);
-    S = std::min(S, 8);
-    S = std::min(S, nkt / std::max(min_tiles, 2));
-    if (S < 2) return r;
-    int tiles = static_cast<int>(cdiv(nkt, S));
-    tiles += tiles & 1;
-    S = static_cast<int>(cdiv(nkt, tiles));
-    if (S < 2) return r;
-    r.S = S; r.tiles = tiles;
-    r.o_bytes = static_cast<size_t>(S) * d->B * d->nq * d->H * d->D * 2;
-    r.bytes = r.o_bytes + static_cast<size_t>(S) * d->B * d->H * d->nq * sizeof(float);
-    return r;
+// Runs plan g: one launch, or for a split key range (g.splits > 1) the split launch into pf_attn_desc.workspace and the merge.
+template <typename T>
+static bool launch_plan(const pf_attn_plan& g, const pf_attn_desc* d, const AttnParams& p, hipStream_t st) {
+    const dim3 grid(g.grid_x, g.grid_y, g.grid_z), block(g.threads);
+    switch (g.kernel) {
+    case 0:
+        if (d->D == 64) hipLaunchKernelGGL((k_attention<T, 64>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((k_attention<T, 32>), grid, block, 0, st, p);
+        return true;
+    case 2: hipLaunchKernelGGL((k_attention_pp<T>), grid, block, 0, st, p); return true;
+    case 3: hipLaunchKernelGGL((k_attention_pp2<T>), grid, block, 0, st, p); return true;
+    case 1: break;
+    default: return false;
+    }
+    if (g.splits == 1) return launch_lds<T>(g, d->D, d->bias != nullptr, p, st);
+    // split key range: S workgroups per query block write normalised partial outputs + their log-sum-exps, one more launch combines them
+    const long rows = static_cast<long>(d->B) * d->nq * d->H;
+    AttnParams ps = p;
+    ps.out = static_cast<unsigned short*>(d->workspace);
+    ps.lse = reinterpret_cast<float*>(ps.out + g.splits * rows * d->D);
+    ps.o_ld = d->H * d->D; ps.o_bs = static_cast<long>(d->nq) * d->H * d->D;
+    ps.split_tiles = g.split_tiles;
+    ps.split_o = rows * d->D;
+    ps.split_lse = rows;
+    if (!launch_lds<T>(g, d->D, d->bias != nullptr, ps, st)) return false;
+    const long total = rows * d->D / 8;
+    hipLaunchKernelGGL((k_attention_merge<T>), dim3(static_cast<unsigned>(cdiv(total, 256))), dim3(256), 0, st, ps.out, ps.lse, g.splits, d->B, d->H, d->D,
+                       d->nq, p.out, d->o_ld, d->o_bs);
+    return true;
 }
 
 }  // namespace pf
 
 using namespace pf;
 
-extern "C" size_t pf_attention_workspace_size(const pf_attn_desc* d) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->nq <= 0 || d->nk <= 0) return 0;
-    const AttnSplit sp = attention_split(d);
-    return sp.S > 1 ? sp.bytes : 0;
-}
-
 extern "C" pf_status pf_attention(const pf_attn_desc* d, void* stream) {
-    PF_REQUIRE(d, "pf_attention: null descriptor");
-    PF_REQUIRE(d->q && d->k && d->vt && d->out, "pf_attention: null pointer");
+    const pf_status v = validate_attn_desc(d, "pf_attention");
+    if (v != PF_OK) return v;
     PF_REQUIRE(d->D == 32 || d->D == 64, "pf_attention: head dim %d unsupported (32 or 64)", d->D);
-    PF_REQUIRE(d->B > 0 && d->H > 0 && d->nq > 0 && d->nk > 0, "pf_attention: bad sizes");
-    PF_REQUIRE(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->o_ld % 4 == 0 && d->vt_ld % 4 == 0,
-               "pf_attention: leading dimensions must be multiples of 8 (q,k) / 4 (out, vt)");
-    PF_REQUIRE(d->vt_ld >= ((d->nk + 31) / 32) * 32, "pf_attention: vt_ld=%d must cover nk=%d rounded up to 32", d->vt_ld, d->nk);
-    PF_REQUIRE(d->q_bs % 8 == 0 && d->k_bs % 8 == 0 && d->vt_bs % 4 == 0 && d->o_bs % 4 == 0, "pf_attention: batch strides misaligned");
-    PF_REQUIRE(aligned16(d->q) && aligned16(d->k) && aligned16(d->vt) && aligned16(d->out), "pf_attention: pointers must be 16-byte aligned");
-    PF_REQUIRE((d->bias == nullptr) == (d->flags == nullptr), "pf_attention: bias and flags come together");
     if (d->bias) {
         PF_REQUIRE(d->nk % 4 == 0 && d->bias_ld % 4 == 0 && d->bias_ld >= d->nk && aligned16(d->bias), "pf_attention: bias needs nk %% 4 == 0 and an aligned ld >= nk");
         PF_REQUIRE(d->flags_ld >= (d->nk + 31) / 32, "pf_attention: flags_ld too small");
     }
+    const pf_attn_plan g = plan_attention_launch(d);
+    PF_REQUIRE(attn_grid_launchable(d, g), "pf_attention: ceil(nq / %d) x H x B = %ld x %d x %d workgroups exceed the grid of kernel %d", g.block_queries,
+               cdiv(d->nq, g.block_queries), d->H, d->B, g.kernel);
+    const AttnTuning& t = attn_tuning();
     AttnParams p;
-    p.q = static_cast<const unsigned short*>(d->q); p.k = static_cast<const unsigned short*>(d->k);
-    p.vt = static_cast<const unsigned short*>(d->vt); p.out = static_cast<unsigned short*>(d->out);
-    p.H = d->H; p.nq = d->nq; p.nk = d->nk;
-    p.q_ld = d->q_ld; p.k_ld = d->k_ld; p.vt_ld = d->vt_ld; p.o_ld = d->o_ld;
-    p.q_bs = d->q_bs; p.k_bs = d->k_bs; p.vt_bs = d->vt_bs; p.o_bs = d->o_bs;
-    p.scale_log2e = d->scale * 1.44269504088896340736f;
+    attn_operands(d, p);
     p.bias = d->bias; p.bias_ld = d->bias_ld; p.flags = d->flags; p.flags_ld = d->flags_ld;
     p.lse = d->lse;
     p.split_tiles = 0; p.split_o = 0; p.split_lse = 0;
-    static const int env_role = attention_occupancy("PF_ATTENTION_PP_ROLE", 3), env_prio = attention_occupancy("PF_ATTENTION_PP_PRIO", 2),
-                     env_xcd = attention_occupancy("PF_ATTENTION_XCD", 1),       // (read once; PF_ATTENTION_PP below is read per call)
-                     env_steady2 = attention_occupancy("PF_ATTENTION_STEADY2", 1);
-    p.steady2 = env_steady2;
-    p.pp_role = env_role;
-    p.pp_prio = env_prio;
-    p.xcd_map = env_xcd;
-    const dim3 grid1(static_cast<unsigned>(cdiv(d->nq, 128) * d->H * d->B));      // k_attention_lds: 1-D, decoded in the kernel
-    dim3 grid(cdiv(d->nq, 128), d->H, d->B), block(256);
-    hipStream_t st = as_stream(stream);
-    // (k_attention_lds addresses K / V^T tiles with 32-bit byte offsets inside one (batch, head) slice)
-    const bool fits32 = !PF_ATTN_BUFLOAD || (static_cast<long>(d->nk + 64) * d->k_ld * 2 < (1L << 31) && static_cast<long>(d->vt_ld) * (d->D + 1) * 2 < (1L << 31));
-    const bool lds = use_lds_attention() && d->vt_ld % 8 == 0 && d->vt_bs % 8 == 0 && fits32;
-    // The experimental ping-pong kernels (PF_ATTENTION_PP = 1 / 2) address K and V^T with 32-bit byte offsets inside a (batch, head) slice.
-    // Evaluated HERE, outside PF_DISPATCH_16: a preprocessor conditional inside that macro's argument had swallowed the K-offset guard
-    // of the one-tile form -- no directives inside macro arguments.
-    const bool pp_fits = static_cast<long>(d->nk) * d->k_ld * 2 < (1L << 31) && static_cast<long>(d->vt_ld) * 64 * 2 < (1L << 31);
-#ifdef PF_ATTN_PP_TIMING
-    const bool pp_lse_ok = true;                                                   // (the timing build writes its stamps over lse)
-#else
-    const bool pp_lse_ok = !d->lse;                                                // (lse = training forward: exact fp32 row sums there)
-#endif
-    const bool pp1_ok = pp_lse_ok && d->nk % 8 == 0 && d->nk >= 128 && pp_fits;
-    const bool pp2_ok = !d->lse && d->nk % 128 == 0 && d->nk >= 256 && pp_fits;
-    PF_DISPATCH_16(d->dtype, "pf_attention",
-        if (lds) {
-            static const int occ64 = attention_occupancy("PF_ATTENTION_OCC", 3), occ32 = attention_occupancy("PF_ATTENTION_OCC32", 4);
-            static const int msum = attention_occupancy("PF_ATTENTION_MSUM", 1);      // 0: softmax row sums on the vector ALU (A/B)
-            static const int msum32 = attention_occupancy("PF_ATTENTION_MSUM32", 0);  // the same for the EPA (D = 32, bias) kernel: 168 registers + 3 spilled
-            const int pingpong = attention_occupancy("PF_ATTENTION_PP", 0);                // (read per call: the tests switch it)      // 0: k_attention_lds for the D = 64 self-attentions too (A/B)
-            if (d->D == 64) {
-                if (d->bias) {                 // (not pipelined it needs 169 registers at three waves per SIMD)
-                    hipLaunchKernelGGL((k_attention_lds<T, 64, true>), grid1, block, 0, st, p);
-                } else if (pingpong == 2 && pp2_ok) {
-                    hipLaunchKernelGGL((k_attention_pp2<T>), dim3(static_cast<unsigned>(cdiv(d->nq, 256) * d->H * d->B)), dim3(512), 0, st, p);
-                } else if (pingpong && pp1_ok) {
-                    hipLaunchKernelGGL((k_attention_pp<T>), dim3(static_cast<unsigned>(cdiv(d->nq, 256) * d->H * d->B)), dim3(512), 0, st, p);
-                } else {
-                    if (occ64 == 2) hipLaunchKernelGGL((k_attention_lds<T, 64, false>), grid1, block, 0, st, p);
-                    else if (msum && !d->lse && d->nk >= 256) hipLaunchKernelGGL((k_attention_lds<T, 64, false, false, 3, true>), grid1, block, 0, st, p);   // (77 text keys: the 4 extra MFMAs of two tiles cost 2 %)
-                    else hipLaunchKernelGGL((k_attention_lds<T, 64, false, false, 3>), grid1, block, 0, st, p);
-                }
-            } else {
-                if (d->bias) {
-                    const AttnSplit sp = attention_split(d);
-                    if (sp.S > 1 && d->workspace && d->workspace_bytes >= sp.bytes && aligned16(d->workspace)) {
-                        // split key range: S workgroups per query block write normalised partial outputs + their log-sum-exps, one more launch combines them
-                        AttnParams ps = p;
-                        ps.out = static_cast<unsigned short*>(d->workspace);
-                        ps.lse = reinterpret_cast<float*>(static_cast<char*>(d->workspace) + sp.o_bytes);
-                        ps.o_ld = d->H * 32; ps.o_bs = static_cast<long>(d->nq) * d->H * 32;
-                        ps.split_tiles = sp.tiles;
-                        ps.split_o = static_cast<long>(d->B) * d->nq * d->H * 32;
-                        ps.split_lse = static_cast<long>(d->B) * d->H * d->nq;
-                        const dim3 grid_s(grid1.x, static_cast<unsigned>(sp.S));
-                        if (occ32 == 5) hipLaunchKernelGGL((k_attention_lds<T, 32, true, false, 5>), grid_s, block, 0, st, ps);
-                        else hipLaunchKernelGGL((k_attention_lds<T, 32, true, false, 4>), grid_s, block, 0, st, ps);
-                        const long total = static_cast<long>(d->B) * d->nq * (d->H * 32 / 8);
-                        hipLaunchKernelGGL((k_attention_merge<T>), dim3(static_cast<unsigned>(cdiv(total, 256))), dim3(256), 0, st, ps.out, ps.lse, sp.S, d->B, d->H, 32,
-                                           d->nq, p.out, d->o_ld, d->o_bs);
-                    }
-                    else if (occ32 == 4) hipLaunchKernelGGL((k_attention_lds<T, 32, true, false, 4>), grid1, block, 0, st, p);
-                    else if (occ32 == 5) hipLaunchKernelGGL((k_attention_lds<T, 32, true, false, 5>), grid1, block, 0, st, p);
-                    else if (msum32 && !d->lse) hipLaunchKernelGGL((k_attention_lds<T, 32, true, true, 3, true>), grid1, block, 0, st, p);
-                    else hipLaunchKernelGGL((k_attention_lds<T, 32, true>), grid1, block, 0, st, p);
-                } else {
-                    if (occ32 == 4) hipLaunchKernelGGL((k_attention_lds<T, 32, false, false, 4>), grid1, block, 0, st, p);
-                    else if (occ32 == 5) hipLaunchKernelGGL((k_attention_lds<T, 32, false, false, 5>), grid1, block, 0, st, p);
-                    else hipLaunchKernelGGL((k_attention_lds<T, 32, false>), grid1, block, 0, st, p);
-                }
-            }
-        } else {
-            if (d->D == 64) hipLaunchKernelGGL((k_attention<T, 64>), grid, block, 0, st, p);
-            else hipLaunchKernelGGL((k_attention<T, 32>), grid, block, 0, st, p);
-        });
+    p.steady2 = t.steady2; p.pp_role = t.pp_role; p.pp_prio = t.pp_prio; p.xcd_map = t.xcd;
+    bool planned = false;
+    PF_DISPATCH_16(d->dtype, "pf_attention", planned = launch_plan<T>(g, d, p, as_stream(stream)));
+    if (!planned) {
+        set_error("pf_attention: no kernel for plan (kernel %d, D %d, pipelined %d, occupancy %d, msum %d)", g.kernel, d->D, g.pipelined, g.occupancy, g.msum);
+        return PF_ERR_LAUNCH;
+    }
     PF_CHECK_LAUNCH("pf_attention");
     return PF_OK;
 }

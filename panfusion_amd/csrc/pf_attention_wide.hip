@@ -36,8 +36,7 @@
 //
 // Replaces the mid-block Attention(heads = 1, dim_head = C) of diffusers' AutoencoderKL (baddbmm + softmax + bmm), reached from
 // models/pano/PanoGenerator.py:213-238 (decode / encode of the panorama and the views).
-#include "pf_common.h"
-#include <atomic>
+#include "pf_attention_plan.h"
 
 namespace pf {
 
@@ -284,23 +283,11 @@ __global__ __launch_bounds__(256, 1) void k_attention_wide(const WideParams p) {
     }
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of one instantiation, set once per device (bitmask of the devices it is set on)
-static pf_status wide_allow_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ULL << dev : 0;
-    if (e == hipSuccess && (done.load(std::memory_order_relaxed) & bit)) return PF_OK;
-    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (e != hipSuccess) { set_error("pf_attention_wide: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return PF_ERR_LAUNCH; }
-    done.fetch_or(bit, std::memory_order_relaxed);
-    return PF_OK;
-}
-
 template <typename T, int D>
 static pf_status launch_wide(const WideParams& p, unsigned blocks, hipStream_t st) {
     static std::atomic<unsigned long long> done{0};
     constexpr size_t lds = wide_lds_bytes(D);
-    const pf_status s = wide_allow_lds(reinterpret_cast<const void*>(k_attention_wide<T, D>), lds, done);
+    const pf_status s = allow_dynamic_lds(reinterpret_cast<const void*>(k_attention_wide<T, D>), lds, done, "pf_attention_wide");
     if (s != PF_OK) return s;
     hipLaunchKernelGGL((k_attention_wide<T, D>), dim3(blocks), dim3(256), lds, st, p);
     return PF_OK;
@@ -311,20 +298,12 @@ static pf_status launch_wide(const WideParams& p, unsigned blocks, hipStream_t s
 using namespace pf;
 
 extern "C" pf_status pf_attention_wide(const pf_attn_desc* d, void* stream) {
-    PF_REQUIRE(d, "pf_attention_wide: null descriptor");
-    PF_REQUIRE(d->q && d->k && d->vt && d->out, "pf_attention_wide: null pointer");
+    const pf_status v = validate_attn_desc(d, "pf_attention_wide");
+    if (v != PF_OK) return v;
     PF_REQUIRE(d->D == 128 || d->D == 256 || d->D == 512, "pf_attention_wide: head dim %d unsupported (128, 256 or 512)", d->D);
-    PF_REQUIRE(d->B > 0 && d->H > 0 && d->nq > 0 && d->nk > 0, "pf_attention_wide: bad sizes");
     PF_REQUIRE(!d->bias && !d->flags, "pf_attention_wide: bias and flags must be NULL (no bias at wide heads)");
     PF_REQUIRE(!d->lse, "pf_attention_wide: lse must be NULL (no backward at wide heads)");
     PF_REQUIRE(!d->workspace, "pf_attention_wide: workspace must be NULL (no key-range split at wide heads)");
-    PF_REQUIRE(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->o_ld % 4 == 0 && d->vt_ld % 4 == 0,
-               "pf_attention_wide: leading dimensions must be multiples of 8 (q,k) / 4 (out, vt)");
-    PF_REQUIRE(d->q_ld >= d->H * d->D && d->k_ld >= d->H * d->D && d->o_ld >= d->H * d->D,
-               "pf_attention_wide: q_ld, k_ld and o_ld must cover H * D = %d columns", d->H * d->D);
-    PF_REQUIRE(d->vt_ld >= ((d->nk + 31) / 32) * 32, "pf_attention_wide: vt_ld=%d must cover nk=%d rounded up to 32", d->vt_ld, d->nk);
-    PF_REQUIRE(d->q_bs % 8 == 0 && d->k_bs % 8 == 0 && d->vt_bs % 4 == 0 && d->o_bs % 4 == 0, "pf_attention_wide: batch strides misaligned");
-    PF_REQUIRE(aligned16(d->q) && aligned16(d->k) && aligned16(d->vt) && aligned16(d->out), "pf_attention_wide: pointers must be 16-byte aligned");
     // The kernel addresses K and V^T with 31-bit byte offsets inside one (batch, head) slice (batch strides are 64-bit), and its grid is 1-D.
     PF_REQUIRE((static_cast<long>(d->nk) + 64) * d->k_ld * 2 < (1L << 31) && static_cast<long>(d->D) * d->vt_ld * 2 < (1L << 31),
                "pf_attention_wide: per-batch operand too large: (nk + 64) * k_ld * 2 = %ld and D * vt_ld * 2 = %ld bytes must stay under 2^31",
@@ -333,12 +312,7 @@ extern "C" pf_status pf_attention_wide(const pf_attn_desc* d, void* stream) {
     PF_REQUIRE(blocks < (1L << 31) && d->nq <= 0x7FFFFFFF - 64,
                "pf_attention_wide: ceil(nq / 64) * H * B = %ld workgroups exceed the 1-D grid (2^31 - 1)", blocks);
     WideParams p;
-    p.q = static_cast<const unsigned short*>(d->q); p.k = static_cast<const unsigned short*>(d->k);
-    p.vt = static_cast<const unsigned short*>(d->vt); p.out = static_cast<unsigned short*>(d->out);
-    p.H = d->H; p.nq = d->nq; p.nk = d->nk;
-    p.q_ld = d->q_ld; p.k_ld = d->k_ld; p.vt_ld = d->vt_ld; p.o_ld = d->o_ld;
-    p.q_bs = d->q_bs; p.k_bs = d->k_bs; p.vt_bs = d->vt_bs; p.o_bs = d->o_bs;
-    p.scale_log2e = d->scale * 1.44269504088896340736f;
+    attn_operands(d, p);
     p.v16 = d->vt_ld % 8 == 0 && d->vt_bs % 8 == 0;
     hipStream_t st = as_stream(stream);
     pf_status s = PF_OK;

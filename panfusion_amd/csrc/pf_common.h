@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
+#include <atomic>
 #include "../../include/panfusion_hip.h"
 
 namespace pf {
@@ -30,6 +32,13 @@ void set_error(const char* fmt, ...);
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+// an integer environment knob (A/B switches for benchmarking; GemmTuning in pf_gemm_params.h, AttnTuning in pf_attention_plan.h)
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// pf_core.hip: lets `kernel` take `bytes` of dynamic LDS on the current device; `done` is that kernel instantiation's own record
+pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done, const char* what);
 
 // ---- 16-bit element types ------------------------------------------------------------------
 // Storage is always a raw 16-bit word; Bf16 / F16 tag types select the conversion and the MFMA.

@@ -1477,19 +1477,6 @@ static inline ProfState prof_snapshot() {
     return s ? *s : ProfState{nullptr, 0};
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of one kernel instantiation, set once per device: `done` is that instantiation's
-// bitmask of the devices it is set on.  The steady-state launch pays a device-id lookup only.
-pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done, const char* what) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ULL << dev : 0;      // (a device past 63 sets it on every launch)
-    if (e == hipSuccess && (done.load(std::memory_order_relaxed) & bit)) return PF_OK;
-    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute failed: %s", what, hipGetErrorString(e)); return PF_ERR_LAUNCH; }
-    done.fetch_or(bit, std::memory_order_relaxed);
-    return PF_OK;
-}
-
 // The launchers below run ONE pass of a plan's kernel: output rows [p.m_begin, p.M) in p.splits K slices (launch_pass combines the slices).
 
 template <typename T, int MREP, int NREP, bool STATS, bool S3, int STAGES, bool A32 = false>

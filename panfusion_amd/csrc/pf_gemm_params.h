@@ -172,10 +172,6 @@ pf_status launch_gemm32(const GemmParams& gp, int dtype, int batch, hipStream_t 
 
 // Every environment knob of the tile GEMMs (A/B switches for benchmarking) with its default.  The members are read ONCE per process
 // (gemm_tuning()); the three that tests switch inside a process are the static accessors below them, read on every call.
-inline int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 struct GemmTuning {
     int deep_ring = env_int("PF_GEMM_DEEP_RING", 1);            // 4-wave grids of at most deep_ring_max_blocks blocks run the four-slot ring, one block per CU
     int deep_ring_max_blocks = env_int("PF_GEMM_DEEP_RING_MAX_BLOCKS", 256);
@@ -207,7 +203,5 @@ void params_from_desc(const pf_conv_desc* d, GemmParams& p);
 // THE plan of a problem: what pf_conv_gemm launches and every query reports.  batch: 4 for the sub-pixel phases, else pf_conv_desc.batch;
 // allow_split: split-K scratch is at hand; want_moments: the launch passes pf_conv_desc.gn_partial.
 pf_conv_plan plan_conv_gemm(const GemmParams& p, int batch, bool allow_split, bool want_moments);
-// pf_gemm.hip: lets `kernel` take `bytes` of dynamic LDS on the current device; `done` is that kernel instantiation's own record
-pf_status allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done, const char* what);
 
 }  // namespace pf

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, ConvDesc, ConvPlan, LinearWsDesc, check
+from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, check
 
 _DT = {torch.bfloat16: PF_BF16, torch.float16: PF_F16, torch.float32: PF_F32}
 
@@ -930,13 +930,8 @@ def conv_out_gn(x, scale, shift, act, wgt_t, bias, cout, wrap=False, out=None):
 
 
 # ---------------------------------------------------------------------------- attention
-def attention(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q_bs, k_bs, vt_bs, o_bs=None,
-              scale=None, bias=None, flags=None, out=None, lse=None):
-    """lse: optional fp32 [B, H, nq] output (log2-domain log-sum-exp of the rows) for attention_bwd."""
-    o_ld = o_ld or H * D
-    o_bs = o_bs if o_bs is not None else nq * o_ld
-    if out is None:
-        out = torch.empty(B, nq, o_ld, device=q.device, dtype=q.dtype)
+def _attn_desc(q, k, vt, out, B, H, D, nq, nk, q_ld, k_ld, vt_ld, o_ld, q_bs, k_bs, vt_bs, o_bs, scale, bias=None, flags=None, lse=None):
+    """pf_attn_desc of a launch, without scratch (attention adds it where the plan asks for some)."""
     d = AttnDesc()
     d.q, d.k, d.vt, d.out = _p(q), _p(k), _p(vt), _p(out)
     d.dtype, d.B, d.H, d.D, d.nq, d.nk = dt(q), B, H, D, nq, nk
@@ -947,10 +942,30 @@ def attention(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q_bs, 
     d.flags, d.flags_ld = _p(flags), (_ld(flags) if flags is not None else 0)
     d.lse = _p(lse)
     d.workspace, d.workspace_bytes = None, 0
+    return d
+
+
+def _attn_plan(d):
+    g = AttnPlan()
+    check(_lib.lib().pf_attention_plan(C.byref(d), C.byref(g)), "pf_attention_plan")
+    return g
+
+
+def attention(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q_bs, k_bs, vt_bs, o_bs=None,
+              scale=None, bias=None, flags=None, out=None, lse=None, want_plan=False):
+    """lse: optional fp32 [B, H, nq] output (log2-domain log-sum-exp of the rows) for attention_bwd.
+    want_plan: launch nothing, allocate nothing, return the library's plan (AttnPlan) of the launch."""
+    o_ld = o_ld or H * D
+    o_bs = o_bs if o_bs is not None else nq * o_ld
+    if out is None and not want_plan:
+        out = torch.empty(B, nq, o_ld, device=q.device, dtype=q.dtype)
+    d = _attn_desc(q, k, vt, out, B, H, D, nq, nk, q_ld, k_ld, vt_ld, o_ld, q_bs, k_bs, vt_bs, o_bs, scale, bias, flags, lse)
+    if want_plan:
+        return _attn_plan(d)
     if bias is not None and lse is None:
         # few query blocks, many keys (the panorama-query direction of an EPA block): scratch that lets the library split the key range over more
-        # workgroups (pf_attn_desc.workspace; 0 bytes = this problem is not split)
-        nbytes = _lib.lib().pf_attention_workspace_size(C.byref(d))
+        # workgroups (pf_attn_desc.workspace; a plan without scratch = this problem is not split)
+        nbytes = _attn_plan(d).workspace_bytes
         if nbytes:
             ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
             d.workspace, d.workspace_bytes = _p(ws), nbytes
@@ -969,14 +984,7 @@ def attention_wide(q, k, vt, B, H, D, nq, nk, *, q_ld, k_ld, vt_ld, o_ld=None, q
     o_bs = o_bs if o_bs is not None else nq * o_ld
     if out is None:
         out = torch.empty(B, nq, o_ld, device=q.device, dtype=q.dtype)
-    d = AttnDesc()
-    d.q, d.k, d.vt, d.out = _p(q), _p(k), _p(vt), _p(out)
-    d.dtype, d.B, d.H, d.D, d.nq, d.nk = dt(q), B, H, D, nq, nk
-    d.q_ld, d.k_ld, d.vt_ld, d.o_ld = q_ld, k_ld, vt_ld, o_ld
-    d.q_bs, d.k_bs, d.vt_bs, d.o_bs = q_bs, k_bs, vt_bs, o_bs
-    d.scale = scale if scale is not None else D ** -0.5
-    d.bias, d.bias_ld, d.flags, d.flags_ld, d.lse = None, 0, None, 0, None
-    d.workspace, d.workspace_bytes = None, 0
+    d = _attn_desc(q, k, vt, out, B, H, D, nq, nk, q_ld, k_ld, vt_ld, o_ld, q_bs, k_bs, vt_bs, o_bs, scale)
     _traced("k_attention_wide", 4.0 * B * H * nq * nk * D,
             lambda: check(_lib.lib().pf_attention_wide(C.byref(d), _stream()), "pf_attention_wide"),
             "B%d H%d D%d nq%d nk%d" % (B, H, D, nq, nk))

@@ -89,13 +89,16 @@ def check_forward(c, ref, out, lse, dtype, what):
         assert float(err.max()) < 2e-4, "%s: lse off by %.3e at (b, head, row) flat index %d" % (name, float(err.max()), int(err.argmax()))
 
 
-def split_desc(c):
-    from panfusion_amd import _lib
-    d = _lib.AttnDesc()
-    d.B, d.H, d.D, d.nq, d.nk, d.bias = c.B, c.H, c.D, c.nq, c.nk, 1
-    d.o_ld = c.H * c.D + 2 * OPAD
-    d.o_bs = c.nq * d.o_ld
-    return _lib.lib().pf_attention_workspace_size(C.byref(d))
+def assert_plan(c, q, k, vt, kw, dtype, S):
+    """The library's plan of the launch run_forward is about to make: the kernel and the rounding arm (MSUM, S splits of the key range) the case claims --
+    the bounds below follow that arm's rounding model."""
+    lse = torch.empty(c.B, c.H, c.nq, device=DEV) if c.lse else None
+    o_ld = c.H * c.D + 2 * OPAD
+    g = ops().attention(q, k, vt, c.B, c.H, c.D, c.nq, c.nk, o_ld=o_ld, o_bs=c.nq * o_ld, lse=lse, want_plan=True, **kw)
+    kernel = 0 if c.arm == "direct" else 1 + c.pp if c.pp else 1
+    msum = c.msum and kernel == 1                             # (the ping-pong kernels always sum on the matrix pipe: no MSUM argument)
+    assert (g.kernel, bool(g.msum), g.splits) == (kernel, msum, S), "%s plans to kernel %d, msum %d, %d splits" % (c.name, g.kernel, g.msum, g.splits)
+    assert (g.workspace_bytes > 0) == (S > 1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -105,13 +108,12 @@ def test_forward(i, dtype, monkeypatch):
     q, k, vt, kw = forward_operands(c, x, dtype)
     if c.pp:
         monkeypatch.setenv("PF_ATTENTION_PP", str(c.pp))
-    if c.S > 1:
-        assert split_desc(c) > 0, "this problem should split its key range"
+    assert_plan(c, q, k, vt, kw, dtype, c.S)
     out, lse = run_forward(c, q, k, vt, kw, dtype)
     check_forward(c, ref, out, lse, dtype, "S%d" % c.S if c.S > 1 else "")
     if c.S > 1:
         monkeypatch.setenv("PF_ATTENTION_SPLIT", "0")
-        assert split_desc(c) == 0
+        assert_plan(c, q, k, vt, kw, dtype, 1)
         out, lse = run_forward(c, q, k, vt, kw, dtype)
         check_forward(c, ref, out, lse, dtype, "S1")
 

@@ -824,9 +824,15 @@ def test_attention_split_key_range(dtype, cfg, monkeypatch):
     kw = dict(q_ld=Cq, k_ld=Cq, vt_ld=ld, q_bs=nq * Cq, k_bs=nk * Cq, vt_bs=Cq * ld, bias=bias.to(DEV), flags=flags.to(DEV))
     d = _lib.AttnDesc()
     d.B, d.H, d.D, d.nq, d.nk, d.o_ld, d.o_bs, d.bias = B, H, D, nq, nk, Cq, nq * Cq, 1
-    assert _lib.lib().pf_attention_workspace_size(C.byref(d)) > 0, "this problem should split"
+    # splits by the rule of DESIGN.md 3.4b, worked by hand: min(8, key tiles // 8) splits of an even number of 64-key tiles (64, 20, 33, 19 tiles)
+    S = {(2, 4, 256, 4096): 8, (1, 10, 128, 1280): 2, (2, 3, 200, 2084): 4, (1, 2, 96, 1156): 2}[cfg]
+    g = ops().attention(q, k, vt, B, H, D, nq, nk, want_plan=True, **kw)
+    assert (g.kernel, g.msum, g.splits) == (1, 0, S) and g.workspace_bytes > 0, "this problem should split its key range %d ways" % S
+    assert _lib.lib().pf_attention_workspace_size(C.byref(d)) == g.workspace_bytes
     out = ops().attention(q, k, vt, B, H, D, nq, nk, **kw)
     monkeypatch.setenv("PF_ATTENTION_SPLIT", "0")
+    g = ops().attention(q, k, vt, B, H, D, nq, nk, want_plan=True, **kw)
+    assert (g.kernel, g.msum, g.splits, g.workspace_bytes) == (1, 0, 1, 0)
     assert _lib.lib().pf_attention_workspace_size(C.byref(d)) == 0
     whole = ops().attention(q, k, vt, B, H, D, nq, nk, **kw)
     want = attn_ref(qf, kf, vf, H, D ** -0.5, bias)
