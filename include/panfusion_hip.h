@@ -511,25 +511,27 @@ pf_status pf_conv_gemm(const pf_conv_desc* desc, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Weight-stationary linear for the token layers of the two finest levels: the nn.Linear layers of their transformer blocks
  * and EPA blocks (models/modules/transformer.py:57-74 to_q / to_k / to_v / to_out, :8-38 GEGLU FeedForward; diffusers
- * BasicTransformerBlock behind models/pano/MVGenModel.py:104-106).  Two shapes:
- *   K == 320, N a multiple of 320 (every mode): a workgroup keeps 320 output channels of the weights in registers and streams
- *             64-token tiles of `a` through LDS;
- *   K == 640, N a multiple of 256 (PF_LWS_16, PF_LWS_GEGLU: q | k and FF1 of the 32^2 level): 256 channels per workgroup,
- *             32-token tiles; N a multiple of 128 only (PF_LWS_16: to_q, N = 640): 128 channels per workgroup;
- *   K == 1280, N a multiple of 128 (PF_LWS_16, PF_LWS_GEGLU: the 16^2 level): 128 channels per workgroup, 16-token tiles.
+ * BasicTransformerBlock behind models/pano/MVGenModel.py:104-106).  A workgroup keeps `chb` output channels of the weights in
+ * registers and streams tiles of `tile_tokens` rows of `a` through LDS.  The shapes it serves (THE rule: pf_linear_ws_plan below is
+ * its one implementation, pf_linear_ws_supported and the launch follow it):
+ *     K     modes                                  N a multiple of    chb    tile_tokens    N / chb
+ *     320   every mode                             320                320    64             <= 32 (PF_LWS_QKV: 3, PF_LWS_F32_LN: 1)
+ *     640   PF_LWS_16, PF_LWS_GEGLU                256                256    32             <= 32
+ *     640   PF_LWS_16 (else), PF_LWS_VT            128                128    32             <= 32
+ *     1280  PF_LWS_16, PF_LWS_GEGLU, PF_LWS_VT     128                128    16             <= 128
+ * and M >= tile_tokens.
  *   PF_LWS_16:    out 16-bit [M][out_ld]      = a w^T + bias
  *   PF_LWS_F32:   out fp32   [M][out_ld]      = a w^T + bias + residual (fp32 [M][res_ld] or NULL)
  *   PF_LWS_GEGLU: out 16-bit [M][out_ld], N/2 columns: w / bias rows interleaved (value_j, gate_j), out = value * gelu(gate)
  *   PF_LWS_QKV:   N == 960 = (q | k | v): out 16-bit [M][out_ld] receives the 640 columns (q | k); V leaves TRANSPOSED as
  *                 out_vt[b][c][key] (b = m / rows_per_batch, key = m % rows_per_batch, row stride vt_ld, batch stride vt_bs):
- *                 the layout pf_attention reads.  rows_per_batch a multiple of 64.
+ *                 the layout pf_attention reads.  rows_per_batch a multiple of tile_tokens that divides M.
  *   PF_LWS_VT:    the whole output TRANSPOSED to out_vt[b][n][key] as in PF_LWS_QKV (the V projection of the 32^2 / 16^2 self-attentions and of
- *                 the EPA blocks: replaces the operand-swapped pf_conv_gemm launch); out unused.  K == 320: N a multiple of 320; K == 640 / 1280:
- *                 N a multiple of 128.  rows_per_batch a multiple of 64 / 32 / 16.
+ *                 the EPA blocks: replaces the operand-swapped pf_conv_gemm launch); out unused.  rows_per_batch as for PF_LWS_QKV.
  *   PF_LWS_F32_LN: N == 320: PF_LWS_F32, and the LayerNorm of the result rides along (the norm2 / norm3 that follow the two
  *                 attention output projections of a BasicTransformerBlock): ln_out 16-bit [M][ln_ld] =
  *                 LayerNorm(out; ln_eps) * ln_gamma + ln_beta -- no separate pass over the stream tensor.
- * a 16-bit [M][a_ld]; w 16-bit [N][K]; bias fp32 [N] or NULL.  pf_linear_ws_supported: 1 if (M, N, K, mode) is served. */
+ * a 16-bit [M][a_ld]; w 16-bit [N][K]; bias fp32 [N] or NULL. */
 typedef struct {
     const void* a; int a_ld;
     const void* w;
@@ -542,7 +544,30 @@ typedef struct {
     int dtype; int mode;
 } pf_linear_ws_desc;
 enum { PF_LWS_16 = 0, PF_LWS_F32 = 1, PF_LWS_GEGLU = 2, PF_LWS_QKV = 3, PF_LWS_F32_LN = 4, PF_LWS_VT = 5 };
+/* The whole plan of a problem: what pf_linear_ws launches, and whether a linear layer should be sent here at all. */
+typedef struct {
+    int supported;       /* 1: the kernel can run (M, N, K, mode) -- the table above; 0: it cannot, every other member is 0             */
+    int preferred;       /* 1: supported, and the linear front ends send the problem here rather than to pf_conv_gemm: dtype 16-bit,
+                          * a_ld >= K and a multiple of 8, rows_per_batch (where stated, PF_LWS_QKV / PF_LWS_VT) a multiple of tile_tokens
+                          * that divides M, M >= PF_LINEAR_WS_MIN_ROWS (8192; K = N = 320: 4 x that) and no knob against it:
+                          * PF_LINEAR_WS=0 (all), PF_LINEAR_WS_K640=0 / PF_LINEAR_WS_K1280=0 (that K), PF_LINEAR_VT=0 (PF_LWS_VT),
+                          * PF_LINEAR_LN=0 (PF_LWS_F32_LN).  The knobs are read once per process.                                        */
+    int k;               /* the reduction width: 320, 640 or 1280                                                                      */
+    int chb;             /* output channels per workgroup: 320, 256 or 128 -- (k, chb, mode) names the kernel instantiation            */
+    int tile_tokens;     /* rows of `a` per LDS ring slot: 64, 32 or 16                                                                */
+    int nblocks;         /* channel blocks: N / chb                                                                                    */
+    int ntiles;          /* token tiles: ceil(M / tile_tokens), dealt out evenly to the token ranges of the grid                       */
+    int splits_per_xcd;  /* > 0: the XCD-grouped grid -- 8 splits_per_xcd token ranges, the nblocks workgroups of a range on one XCD   */
+    int flat_splits;     /* > 0: the flat grid -- flat_splits token ranges, workgroup b = (range b / nblocks, channel block b % nblocks);
+                          * taken where the grouped grid would fill fewer than 200 of the 256 CUs.  Exactly one of the two is nonzero.   */
+    int counted;         /* 1: the kernel waits for a tile's loads by count; 0 (PF_LWS_COUNTED=0): it drains all memory operations     */
+} pf_lws_plan;
+/* Reads only the scalar members M, N, K, mode, dtype, a_ld, rows_per_batch (0: not stated, not checked) -- never a pointer; PF_ERR_ARG
+ * for a NULL argument only: an unsupported problem has a plan with supported = 0. */
+pf_status pf_linear_ws_plan(const pf_linear_ws_desc* desc, pf_lws_plan* out);
+/* pf_linear_ws_plan's `supported` for (M, N, K, mode). */
 int pf_linear_ws_supported(long M, int N, int K, int mode);
+/* Launches every supported problem, preferred or not. */
 pf_status pf_linear_ws(const pf_linear_ws_desc* desc, void* stream);
 
 /* 3x3 convolutions with 4 input or 4 output channels at the UNet boundary:

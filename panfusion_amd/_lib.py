@@ -80,6 +80,14 @@ class LinearWsDesc(C.Structure):
     ]
 
 
+class LwsPlan(C.Structure):
+    """pf_lws_plan"""
+    _fields_ = [
+        ("supported", c_int), ("preferred", c_int), ("k", c_int), ("chb", c_int), ("tile_tokens", c_int), ("nblocks", c_int),
+        ("ntiles", c_int), ("splits_per_xcd", c_int), ("flat_splits", c_int), ("counted", c_int),
+    ]
+
+
 class AttnBwdDesc(C.Structure):
     """pf_attn_bwd_desc"""
     _fields_ = [
@@ -176,6 +184,7 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     "pf_debug_gemm_profile": (c_int, [c_void_p, c_long]),
     "pf_linear_ws_supported": (c_int, [c_long, c_int, c_int, c_int]),
+    "pf_linear_ws_plan": (c_int, [C.POINTER(LinearWsDesc), C.POINTER(LwsPlan)]),
     "pf_linear_ws": (c_int, [C.POINTER(LinearWsDesc), c_void_p]),
     "pf_conv_in": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                            c_void_p, c_void_p]),

@@ -1,8 +1,10 @@
 // Weight-stationary linear layers for the token streams of the two finest UNet levels (gfx950 / CDNA4).
 //
-//   out[m][n] = sum_k a[m][k] * w[n][k]  (+ bias[n]) (+ residual[m][n])        K = 320, N a multiple of 320   (64^2 level, every mode)
-//                                                                                K = 640, N a multiple of 256   (32^2 level: 16-bit and GEGLU outputs; of 128: 16-bit)
-//                                                                                K = 1280, N a multiple of 128  (16^2 level: 16-bit and GEGLU outputs)
+//   out[m][n] = sum_k a[m][k] * w[n][k]  (+ bias[n]) (+ residual[m][n])        K = 320 / 640 / 1280: the 64^2 / 32^2 / 16^2 level
+//
+// Which (M, N, K, mode) are served, by which instantiation and grid split, is decided in ONE place: plan_linear_ws
+// (pf_linear_ws_plan.hip; the table is written down at pf_linear_ws_desc in include/panfusion_hip.h).  This file holds the kernel and the
+// launch of a plan.
 //
 // Why a second GEMM structure: at K = 320 the tile kernel of pf_gemm.hip (256 x 160 tile, K loop of 5 steps) spends
 // 6.4 k clocks of a 32 k-clock tile in the matrix pipes (profiles/r4a_timeline.txt): 260 KB of operands per tile enter
@@ -21,10 +23,7 @@
 //
 // Replaces cuBLAS behind the nn.Linear layers of diffusers' BasicTransformerBlock / the reference's
 // models/modules/transformer.py:57-74 (to_q / to_k / to_v / to_out), :8-38 (GEGLU FeedForward) at C = 320.
-#include "pf_common.h"
-#include <atomic>
-#include <stdlib.h>
-#include <algorithm>
+#include "pf_linear_ws_plan.h"
 
 namespace pf {
 
@@ -407,7 +406,7 @@ __device__ __forceinline__ void lws_wave(const LwsParams& p, unsigned short* sme
     }
 }
 
-template <typename T, int MODE, bool COUNTED, int K, int CHB = (K == 320 ? 320 : K == 640 ? 256 : 128)>
+template <typename T, int MODE, bool COUNTED, int K, int CHB>
 __global__ __launch_bounds__(512, 1) void k_linear_ws(const LwsParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
     const int t = threadIdx.x, lane = t & 63;
@@ -440,55 +439,52 @@ __global__ __launch_bounds__(512, 1) void k_linear_ws(const LwsParams p) {
     }
 }
 
-template <typename T, int MODE, bool COUNTED, int K, int CHB>
-static pf_status lws_launch_c(const LwsParams& p, hipStream_t st) {
+template <typename T, int MODE, int K, int CHB>
+static pf_status lws_launch(const LwsParams& p, bool counted, hipStream_t st) {
     const size_t smem = static_cast<size_t>(LWS_STAGES) * LWS_STAGE_ELEMS * 2 + 8 * LWS_STG_BYTES + LWS_LN_BYTES;
-    // per (instantiation, device): the attribute is a property of the function ON a device; the status is checked (a failed
-    // call used to surface as an opaque launch failure).  std::atomic: concurrent first launches both set it, harmlessly.
-    static std::atomic<unsigned long long> attr_devs{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ULL << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_ws<T, MODE, COUNTED, K, CHB>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-        PF_REQUIRE(e == hipSuccess, "pf_linear_ws: the device does not grant %zu bytes of LDS per workgroup (%s)", smem, hipGetErrorString(e));
-        attr_devs.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_linear_ws<T, MODE, COUNTED, K, CHB>), dim3(256), dim3(512), smem, st, p);
+    static std::atomic<unsigned long long> lds_ok[2];             // per (instantiation, device): the attribute belongs to the function ON a device
+    const void* kernel = counted ? reinterpret_cast<const void*>(k_linear_ws<T, MODE, true, K, CHB>) : reinterpret_cast<const void*>(k_linear_ws<T, MODE, false, K, CHB>);
+    const pf_status s = allow_dynamic_lds(kernel, smem, lds_ok[counted], "pf_linear_ws");
+    if (s != PF_OK) return s;
+    if (counted) hipLaunchKernelGGL((k_linear_ws<T, MODE, true, K, CHB>), dim3(256), dim3(512), smem, st, p);
+    else hipLaunchKernelGGL((k_linear_ws<T, MODE, false, K, CHB>), dim3(256), dim3(512), smem, st, p);
     PF_CHECK_LAUNCH("pf_linear_ws");
     return PF_OK;
 }
-template <typename T, int MODE, int K = 320, int CHB = (K == 320 ? 320 : K == 640 ? 256 : 128)>
-static pf_status lws_launch(const LwsParams& p, hipStream_t st) {
-    static const bool counted = !(getenv("PF_LWS_COUNTED") && atoi(getenv("PF_LWS_COUNTED")) == 0);
-    return counted ? lws_launch_c<T, MODE, true, K, CHB>(p, st) : lws_launch_c<T, MODE, false, K, CHB>(p, st);
+
+// The k_linear_ws instantiation a plan names, as (K, channels per workgroup, mode): these thirteen are the ones that exist.
+constexpr int lws_class(int k, int chb, int mode) { return (k << 12) | (chb << 3) | mode; }
+template <typename T>
+static pf_status launch_plan(const pf_lws_plan& g, int mode, const LwsParams& p, hipStream_t st) {
+    switch (lws_class(g.k, g.chb, mode)) {
+    case lws_class(320, 320, PF_LWS_16): return lws_launch<T, LWS_16, 320, 320>(p, g.counted, st);
+    case lws_class(320, 320, PF_LWS_F32): return lws_launch<T, LWS_F32, 320, 320>(p, g.counted, st);
+    case lws_class(320, 320, PF_LWS_GEGLU): return lws_launch<T, LWS_GEGLU, 320, 320>(p, g.counted, st);
+    case lws_class(320, 320, PF_LWS_QKV): return lws_launch<T, LWS_QKV, 320, 320>(p, g.counted, st);
+    case lws_class(320, 320, PF_LWS_F32_LN): return lws_launch<T, LWS_F32_LN, 320, 320>(p, g.counted, st);
+    case lws_class(320, 320, PF_LWS_VT): return lws_launch<T, LWS_VT, 320, 320>(p, g.counted, st);
+    case lws_class(640, 256, PF_LWS_16): return lws_launch<T, LWS_16, 640, 256>(p, g.counted, st);
+    case lws_class(640, 256, PF_LWS_GEGLU): return lws_launch<T, LWS_GEGLU, 640, 256>(p, g.counted, st);
+    case lws_class(640, 128, PF_LWS_16): return lws_launch<T, LWS_16, 640, 128>(p, g.counted, st);
+    case lws_class(640, 128, PF_LWS_VT): return lws_launch<T, LWS_VT, 640, 128>(p, g.counted, st);
+    case lws_class(1280, 128, PF_LWS_16): return lws_launch<T, LWS_16, 1280, 128>(p, g.counted, st);
+    case lws_class(1280, 128, PF_LWS_GEGLU): return lws_launch<T, LWS_GEGLU, 1280, 128>(p, g.counted, st);
+    case lws_class(1280, 128, PF_LWS_VT): return lws_launch<T, LWS_VT, 1280, 128>(p, g.counted, st);
+    }
+    set_error("pf_linear_ws: no kernel for plan (K %d, %d channels per workgroup, mode %d)", g.k, g.chb, mode);   // (a planner bug)
+    return PF_ERR_LAUNCH;
 }
 
 }  // namespace pf
 
-extern "C" int pf_linear_ws_supported(long M, int N, int K, int mode) {
-    if (K == 640) {               // 256-channel workgroups: 16-bit and GEGLU outputs (FF1, q | k of the 32^2 level);
-        if (N <= 0 || M < 32) return 0;                                        // 128-channel workgroups: 16-bit output (to_q: N = 640).  (fp32 + residual
-        if (N % 256 == 0 && N / 256 <= 32 && (mode == PF_LWS_16 || mode == PF_LWS_GEGLU)) return 1;   // was built and measured: 98 vs 89 us for the tile kernel)
-        return N % 128 == 0 && N / 128 <= 32 && (mode == PF_LWS_16 || mode == PF_LWS_VT);
-    }
-    if (K == 1280)                // 16-token tiles, 128-channel workgroups: 16-bit and GEGLU outputs (q | k, to_q, FF1 of the 16^2 level)
-        return N > 0 && N % 128 == 0 && N / 128 <= 128 && M >= 16 && (mode == PF_LWS_16 || mode == PF_LWS_GEGLU || mode == PF_LWS_VT);
-    if (K != 320 || N <= 0 || N % 320 != 0 || M < 64) return 0;
-    const int nb = N / 320;
-    if (nb > 32) return 0;
-    if (mode == PF_LWS_QKV && nb != 3) return 0;
-    if (mode == PF_LWS_F32_LN && nb != 1) return 0;
-    return 1;
-}
+using namespace pf;
 
 extern "C" pf_status pf_linear_ws(const pf_linear_ws_desc* d, void* stream) {
-    using namespace pf;
     PF_REQUIRE(d != nullptr, "pf_linear_ws: null descriptor");
     PF_REQUIRE(d->a && d->w && (d->out || d->mode == PF_LWS_VT), "pf_linear_ws: null operand");
-    PF_REQUIRE(pf_linear_ws_supported(d->M, d->N, d->K, d->mode), "pf_linear_ws: needs K == 320, N a multiple of 320 (<= 32 blocks; q|k|v: N == 960), M >= 64 -- or K == 640 with N a multiple of 256 (16-bit / GEGLU output) or of 128 (16-bit output), or K == 1280 with N a multiple of 128 (16-bit / GEGLU output) (got M %ld N %d K %d mode %d)",
-               static_cast<long>(d->M), d->N, d->K, d->mode);
     PF_REQUIRE(d->mode >= PF_LWS_16 && d->mode <= PF_LWS_VT, "pf_linear_ws: unknown mode %d", d->mode);
+    const pf_lws_plan g = plan_linear_ws(d->M, d->N, d->K, d->mode, d->dtype, d->a_ld, d->rows_per_batch);   // (every supported problem is launched, preferred or not)
+    PF_REQUIRE(g.supported, "pf_linear_ws: M %d N %d K %d mode %d is none of the shapes at pf_linear_ws_desc (include/panfusion_hip.h)", d->M, d->N, d->K, d->mode);
     PF_REQUIRE(d->a_ld >= d->K && d->a_ld % 8 == 0 && aligned16(d->a) && aligned16(d->w) && (!d->out || aligned16(d->out)), "pf_linear_ws: operands must be 16-byte aligned, a_ld a multiple of 8");
     PF_REQUIRE(static_cast<long>(d->M) * d->a_ld * 2 < (2L << 30), "pf_linear_ws: activation matrix must be smaller than 2 GiB");
     PF_REQUIRE(!d->bias || aligned16(d->bias), "pf_linear_ws: bias must be 16-byte aligned");
@@ -500,19 +496,13 @@ extern "C" pf_status pf_linear_ws(const pf_linear_ws_desc* d, void* stream) {
     else
         PF_REQUIRE(!d->residual, "pf_linear_ws: a residual needs mode PF_LWS_F32");
     if (d->mode == PF_LWS_F32_LN)
-        PF_REQUIRE(d->N == 320 && d->ln_gamma && d->ln_beta && d->ln_out && aligned16(d->ln_gamma) && aligned16(d->ln_beta) && aligned16(d->ln_out) &&
+        PF_REQUIRE(d->ln_gamma && d->ln_beta && d->ln_out && aligned16(d->ln_gamma) && aligned16(d->ln_beta) && aligned16(d->ln_out) &&
                    d->ln_ld >= 320 && d->ln_ld % 8 == 0 && d->ln_eps > 0.f,
-                   "pf_linear_ws: the LayerNorm mode needs N == 320 (a whole row per workgroup), gamma / beta / ln_out 16-byte aligned");
-    if (d->mode == PF_LWS_VT) {
-        const int tok = d->K == 1280 ? 16 : d->K == 640 ? 32 : 64;
-        PF_REQUIRE(d->out_vt && aligned16(d->out_vt) && d->rows_per_batch > 0 && d->rows_per_batch % tok == 0 && d->M % d->rows_per_batch == 0 &&
+                   "pf_linear_ws: the LayerNorm mode needs gamma / beta / ln_out 16-byte aligned, ln_ld a multiple of 8, ln_eps > 0");
+    if (d->mode == PF_LWS_VT || d->mode == PF_LWS_QKV)
+        PF_REQUIRE(d->out_vt && aligned16(d->out_vt) && d->rows_per_batch > 0 && d->rows_per_batch % g.tile_tokens == 0 && d->M % d->rows_per_batch == 0 &&
                    d->vt_ld >= d->rows_per_batch && d->vt_ld % 8 == 0 && d->vt_bs % 8 == 0,
-                   "pf_linear_ws: the transposed mode needs out_vt with 16-byte aligned key runs and batches of a multiple of %d tokens", tok);
-    }
-    if (d->mode == PF_LWS_QKV)
-        PF_REQUIRE(d->out_vt && aligned16(d->out_vt) && d->rows_per_batch > 0 && d->rows_per_batch % 64 == 0 && d->M % d->rows_per_batch == 0 &&
-                   d->vt_ld >= d->rows_per_batch && d->vt_ld % 8 == 0 && d->vt_bs % 8 == 0,
-                   "pf_linear_ws: q|k|v mode needs out_vt with 16-byte aligned key runs and batches of a multiple of 64 tokens");
+                   "pf_linear_ws: a transposed output needs out_vt with 16-byte aligned key runs and batches of a multiple of %d tokens", g.tile_tokens);
     LwsParams p;
     p.a = static_cast<const unsigned short*>(d->a); p.a_ld = d->a_ld;
     p.w = static_cast<const unsigned short*>(d->w);
@@ -521,34 +511,9 @@ extern "C" pf_status pf_linear_ws(const pf_linear_ws_desc* d, void* stream) {
     p.out_vt = static_cast<unsigned short*>(d->out_vt); p.vt_ld = d->vt_ld; p.rows_per_batch = d->rows_per_batch; p.vt_bs = d->vt_bs;
     p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.ln_eps = d->ln_eps; p.ln_out = static_cast<unsigned short*>(d->ln_out); p.ln_ld = d->ln_ld;
     p.M = d->M; p.N = d->N;
-    const bool k640 = d->K == 640, k1280 = d->K == 1280;
-    const bool chb128 = k640 && (d->mode == PF_LWS_VT || !(d->N % 256 == 0 && (d->mode == PF_LWS_16 || d->mode == PF_LWS_GEGLU)));
-    p.nblocks = d->N / (chb128 || k1280 ? 128 : k640 ? 256 : 320);
-    p.splits_per_xcd = 32 / p.nblocks;
-    p.flat_splits = 8 * p.splits_per_xcd * p.nblocks >= 200 ? 0 : std::max(1, 256 / p.nblocks);
-    p.ntiles = static_cast<int>(cdiv(d->M, k1280 ? 16 : k640 ? 32 : 64));
+    p.nblocks = g.nblocks; p.splits_per_xcd = g.splits_per_xcd; p.flat_splits = g.flat_splits; p.ntiles = g.ntiles;
     p.a_bytes = static_cast<unsigned>(static_cast<long>(d->M) * d->a_ld * 2);
-    hipStream_t st = as_stream(stream);
-#define PF_LWS_MODE(MODE) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, MODE>(p, st)))
-    if (k1280 && d->mode == PF_LWS_VT) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_VT, 1280>(p, st)));
-    if (chb128 && d->mode == PF_LWS_VT) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_VT, 640, 128>(p, st)));
-    if (k1280) {
-        if (d->mode == PF_LWS_GEGLU) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_GEGLU, 1280>(p, st)));
-        PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_16, 1280>(p, st)));
-    }
-    if (chb128) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_16, 640, 128>(p, st)));
-    if (k640) {
-        if (d->mode == PF_LWS_GEGLU) PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_GEGLU, 640>(p, st)));
-        PF_DISPATCH_16(d->dtype, "pf_linear_ws", return (lws_launch<T, LWS_16, 640>(p, st)));
-    }
-    switch (d->mode) {
-        case PF_LWS_16: PF_LWS_MODE(LWS_16);
-        case PF_LWS_F32: PF_LWS_MODE(LWS_F32);
-        case PF_LWS_GEGLU: PF_LWS_MODE(LWS_GEGLU);
-        case PF_LWS_F32_LN: PF_LWS_MODE(LWS_F32_LN);
-        case PF_LWS_VT: PF_LWS_MODE(LWS_VT);
-        default: PF_LWS_MODE(LWS_QKV);
-    }
-#undef PF_LWS_MODE
+    PF_DISPATCH_16(d->dtype, "pf_linear_ws", return launch_plan<T>(g, d->mode, p, as_stream(stream)));
     return PF_OK;
 }
+

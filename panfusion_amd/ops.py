@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, check
+from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, LwsPlan, check
 
 _DT = {torch.bfloat16: PF_BF16, torch.float16: PF_F16, torch.float32: PF_F32}
 
@@ -741,43 +741,62 @@ def gemm_workspace_bytes(a0, w, n_out, *, a1=None, n_img=1, h_in=1, w_in=None, k
     return max(_conv_plan(d, 0).workspace_bytes, _conv_plan(d, 1).workspace_bytes)
 
 
-# ---- weight-stationary linear (pf_linear_ws): the C = 320 token layers
+# ---- weight-stationary linear (pf_linear_ws): the token layers of the three finest levels.  WHICH linear goes there is the library's
+# decision (pf_linear_ws_plan, include/panfusion_hip.h -- shapes, thresholds and the PF_LINEAR_* knobs live there, read once per
+# process): the front ends below map a call to a mode and ask.
 LWS_16, LWS_F32, LWS_GEGLU, LWS_QKV, LWS_F32_LN, LWS_VT = 0, 1, 2, 3, 4, 5
-LINEAR_WS = os.environ.get("PF_LINEAR_WS", "1") != "0"          # A/B: 0 = every linear on the tile kernel (pf_conv_gemm)
-LINEAR_WS_K640 = os.environ.get("PF_LINEAR_WS_K640", "1") != "0"   # A/B: 0 = the K = 640 layers (32^2 level: FF1, q | k) stay on the tile kernel
-LINEAR_WS_K1280 = os.environ.get("PF_LINEAR_WS_K1280", "1") != "0"  # A/B: 0 = the K = 1280 layers (16^2 level: FF1, q | k, to_q) stay on the tile kernel
-LINEAR_VT = os.environ.get("PF_LINEAR_VT", "1") != "0"              # A/B: 0 = V^T projections by the operand-swapped tile GEMM (linear_t)
-LINEAR_WS_MIN_ROWS = int(os.environ.get("PF_LINEAR_WS_MIN_ROWS", "8192"))   # fewer 64-token tiles than workgroups: the tile kernel
+_LWS_PLANS = _PlanCache()        # the scalar members of a pf_linear_ws_desc -> its LwsPlan (nothing the plan reads changes inside a process)
+
+
+def _lws_key(x, w, mode, rows_per_batch=0):
+    """The scalar members of the pf_linear_ws_desc of a call, (M, N, K, mode, a_ld, dtype, rows_per_batch) -- or None where the tensors
+    themselves rule the kernel out: x not [rows, K] with unit inner stride, w not contiguous."""
+    if x.dim() != 2 or x.stride(1) != 1 or not w.is_contiguous():
+        return None
+    return (x.shape[0], w.shape[0], x.shape[1], mode, x.stride(0), _DT.get(x.dtype, -1), rows_per_batch)
+
+
+def _lws_desc(key):
+    """A pf_linear_ws_desc with the scalar members of _lws_key (the pointers are the caller's)."""
+    d = LinearWsDesc()
+    d.M, d.N, d.K, d.mode, d.a_ld, d.dtype, d.rows_per_batch = key
+    return d
+
+
+def _lws_plan(key):
+    """pf_linear_ws_plan of the problem _lws_key describes, asked once per problem."""
+    plans = _LWS_PLANS.plans
+    g = plans.get(key)
+    if g is None:
+        if len(plans) >= _LWS_PLANS.LIMIT:
+            plans.pop(next(iter(plans)))
+        g = plans[key] = LwsPlan()
+        check(_lib.lib().pf_linear_ws_plan(C.byref(_lws_desc(key)), C.byref(g)), "pf_linear_ws_plan")
+    return g
+
+
+def _lws_preferred(x, w, mode, rows_per_batch=0):
+    key = _lws_key(x, w, mode, rows_per_batch)
+    return key is not None and _lws_plan(key).preferred != 0
 
 
 def linear_ws_ok(rows, N, K, mode, x=None):
-    """Does pf_linear_ws serve this problem?  K == 320 (N a multiple of 320, every mode), K == 640 (N a multiple of 256: 16-bit and GEGLU
-    outputs; of 128: 16-bit) or K == 1280 (N a multiple of 128: 16-bit and GEGLU), and enough token tiles to stream."""
-    if not LINEAR_WS or rows < LINEAR_WS_MIN_ROWS:
-        return False
-    if K == 640:                  # 256-channel workgroups (16-bit, GEGLU) or 128-channel workgroups (16-bit: to_q, N = 640)
-        if not LINEAR_WS_K640 or not ((N % 256 == 0 and mode in (LWS_16, LWS_GEGLU)) or (N % 128 == 0 and mode in (LWS_16, LWS_VT))):
-            return False
-    elif K == 1280:               # 16^2 level: 128-channel workgroups, 16-token tiles (16-bit, GEGLU)
-        if not LINEAR_WS_K1280 or N % 128 or mode not in (LWS_16, LWS_GEGLU, LWS_VT):
-            return False
-    elif K != 320 or N % 320:
-        return False
-    elif N == 320 and rows < 4 * LINEAR_WS_MIN_ROWS:     # one channel block: 256 token ranges -- under 2 tiles each the tile kernel wins
-        return False                                      # (M = 16384: 0.88 - 0.94 x; q | k | v and FF1 win from 8192 rows, profiles/r4_lws_notes.txt)
-    if x is not None and (x.dtype not in (torch.float16, torch.bfloat16) or x.stride(-1) != 1 or x.stride(-2) % 8):
-        return False
-    return bool(_lib.lib().pf_linear_ws_supported(rows, N, K, mode))
+    """Do the front ends below send this problem to pf_linear_ws (x: the activations, for their dtype and row stride)?"""
+    return _lws_plan((rows, N, K, mode) + ((K, PF_BF16) if x is None else (x.stride(-2) if x.stride(-1) == 1 else 0, _DT.get(x.dtype, -1))) + (0,)).preferred != 0
 
 
-def linear_ws(x, w, mode, bias=None, residual=None, out=None, out_vt=None, rows_per_batch=0, ln=None):
-    """pf_linear_ws: x [rows, K] 16-bit, w [N, K] (K = 320; K = 640 for the 16-bit and GEGLU modes).  mode LWS_16 -> [rows, N] 16-bit; LWS_F32 -> fp32 [rows, N] (+ fp32 residual);
+def linear_ws(x, w, mode, bias=None, residual=None, out=None, out_vt=None, rows_per_batch=0, ln=None, want_plan=False):
+    """pf_linear_ws: x [rows, K] 16-bit, w [N, K] (the shapes at pf_linear_ws_desc, include/panfusion_hip.h).  mode LWS_16 -> [rows, N] 16-bit; LWS_F32 -> fp32 [rows, N] (+ fp32 residual);
     LWS_GEGLU -> [rows, N/2]; LWS_QKV (N = 960) -> ((q | k) [rows, 640], V^T [rows / rows_per_batch, 320, rows_per_batch]);
-    LWS_F32_LN (N = 320, ln = (gamma, beta, eps)) -> (fp32 [rows, 320], LayerNorm of it in 16 bit [rows, 320]); LWS_VT (K = 640 / 1280)
-    -> the output transposed, [rows / rows_per_batch, N, rows_per_batch]."""
-    rows, K = x.shape
-    N = w.shape[0]
-    d = LinearWsDesc()
+    LWS_F32_LN (N = 320, ln = (gamma, beta, eps)) -> (fp32 [rows, 320], LayerNorm of it in 16 bit [rows, 320]); LWS_VT
+    -> the output transposed, [rows / rows_per_batch, N, rows_per_batch].
+    want_plan: launch nothing, allocate nothing, return the library's plan (LwsPlan) of the launch."""
+    key = _lws_key(x, w, mode, rows_per_batch)
+    assert key is not None, "pf_linear_ws: x must be [rows, K] with a contiguous innermost dimension, w contiguous"
+    if want_plan:
+        return _lws_plan(key)
+    rows, N, K = key[:3]
+    d = _lws_desc(key)
     ln_out = None
     if mode == LWS_F32_LN:
         ln_out = torch.empty(rows, N, device=x.device, dtype=x.dtype)
@@ -788,22 +807,21 @@ def linear_ws(x, w, mode, bias=None, residual=None, out=None, out_vt=None, rows_
             out = torch.empty(rows, 640, device=x.device, dtype=x.dtype)
         if out_vt is None:
             out_vt = torch.empty(nb, 320, rows_per_batch, device=x.device, dtype=x.dtype)
-        d.out_vt, d.vt_ld, d.rows_per_batch, d.vt_bs = _p(out_vt), out_vt.stride(1), rows_per_batch, out_vt.stride(0)
+        d.out_vt, d.vt_ld, d.vt_bs = _p(out_vt), out_vt.stride(1), out_vt.stride(0)
     elif mode == LWS_VT:
         nb = rows // rows_per_batch
         if out_vt is None:
             out_vt = torch.empty(nb, N, rows_per_batch, device=x.device, dtype=x.dtype)
-        d.out_vt, d.vt_ld, d.rows_per_batch, d.vt_bs = _p(out_vt), out_vt.stride(1), rows_per_batch, out_vt.stride(0)
+        d.out_vt, d.vt_ld, d.vt_bs = _p(out_vt), out_vt.stride(1), out_vt.stride(0)
     elif out is None:
         out = torch.empty(rows, N // 2 if mode == LWS_GEGLU else N, device=x.device,
                           dtype=torch.float32 if mode in (LWS_F32, LWS_F32_LN) else x.dtype)
-    d.a, d.a_ld, d.w, d.bias = _p(x), _ld(x), _p(w), _p(bias)
+    d.a, d.w, d.bias = _p(x), _p(w), _p(bias)
     d.residual, d.res_ld = _p(residual), (_ld(residual) if residual is not None else 0)
     for buf in (out, out_vt):            # caller-supplied buffers: GroupNorm moments they carried described their OLD contents
         if buf is not None:
             _written(buf)
     d.out, d.out_ld = _p(out), (_ld(out) if out is not None else 0)
-    d.M, d.N, d.K, d.dtype, d.mode = rows, N, K, dt(x), mode
     if TRACE is None:
         check(_lib.lib().pf_linear_ws(C.byref(d), _stream()), "pf_linear_ws")
     else:
@@ -814,34 +832,29 @@ def linear_ws(x, w, mode, bias=None, residual=None, out=None, out_vt=None, rows_
 
 def linear_vt(x, w, n_batch):
     """The V projection of a self-attention written transposed, x [n_batch * nk, K] layer-normed tokens, w [N, K] -> V^T [n_batch, N, nk] (what
-    pf_attention reads) -- on the weight-stationary kernel where it serves the shape, or None: the caller then takes the operand-swapped tile GEMM
-    (linear_t)."""
-    rows, K = x.shape
+    pf_attention reads) -- on the weight-stationary kernel where the library prefers it for the shape, or None: the caller then takes the
+    operand-swapped tile GEMM (linear_t)."""
+    rows = x.shape[0]
     nk = rows // n_batch
-    if not LINEAR_VT:
-        return None
-    if nk * n_batch != rows or nk % (16 if K == 1280 else 32 if K == 640 else 64) or not w.is_contiguous() or not linear_ws_ok(rows, w.shape[0], K, LWS_VT, x):
+    if nk * n_batch != rows or not _lws_preferred(x, w, LWS_VT, nk):
         return None
     return linear_ws(x, w, LWS_VT, rows_per_batch=nk)
 
 
 def linear_ln(x, w, bias, residual, gamma, beta, eps):
-    """out = x w^T + bias + residual (fp32 stream) together with LayerNorm(out) in 16 bit, in ONE launch where pf_linear_ws serves
-    the shape (C = 320: the row is complete inside a workgroup) -> (out, ln_out); (out, None) otherwise -- the caller then runs
+    """out = x w^T + bias + residual (fp32 stream) together with LayerNorm(out) in 16 bit, in ONE launch where pf_linear_ws is preferred
+    for the shape (C = 320: the row is complete inside a workgroup) -> (out, ln_out); (out, None) otherwise -- the caller then runs
     ops.layernorm itself."""
-    rows, K = x.shape
-    if (w.shape[0] == 320 and x.dim() == 2 and w.is_contiguous() and residual is not None and residual.dtype == torch.float32
-            and linear_ws_ok(rows, 320, K, LWS_F32_LN, x) and os.environ.get("PF_LINEAR_LN", "1") != "0"):
+    if residual is not None and residual.dtype == torch.float32 and _lws_preferred(x, w, LWS_F32_LN):
         return linear_ws(x, w, LWS_F32_LN, bias=bias, residual=residual, ln=(gamma, beta, eps))
     return linear(x, w, bias=bias, residual=residual), None
 
 
 def linear_qkv(x, wqkv, n_batch):
     """Self-attention projections in one launch: x [n_batch * nk, 320] layer-normed tokens, wqkv [960, 320] = (q | k | v)
-    -> ((q | k) [rows, 640], V^T [n_batch, 320, nk]), or None when pf_linear_ws does not serve the shape."""
-    rows = x.shape[0]
-    nk = rows // n_batch
-    if wqkv.shape[0] != 960 or nk % 64 or not linear_ws_ok(rows, 960, x.shape[1], LWS_QKV, x):
+    -> ((q | k) [rows, 640], V^T [n_batch, 320, nk]), or None where pf_linear_ws is not preferred for the shape."""
+    nk = x.shape[0] // n_batch
+    if not _lws_preferred(x, wqkv, LWS_QKV, nk):
         return None
     return linear_ws(x, wqkv, LWS_QKV, rows_per_batch=nk)
 
@@ -850,9 +863,9 @@ def linear(x, w, bias=None, residual=None, out=None, out_dtype=None, geglu=False
     """x [rows, K] 16-bit, w [N, K] 16-bit.  geglu: w / bias rows interleaved (value_j, gate_j),
     returns [rows, N/2] = value * gelu(gate).  gn_stats: see conv_gemm (the moment runs are runs of token rows; the
     consumer's images must be whole runs, which groupnorm_scale_shift's entry point checks).
-    The C = 320 layers with enough tokens go to the weight-stationary kernel (pf_linear_ws)."""
+    The layers the library prefers on the weight-stationary kernel (pf_linear_ws_plan) go there."""
     rows, K = x.shape
-    if not (split_out or gn_stats) and x.dim() == 2 and w.is_contiguous():
+    if not (split_out or gn_stats):
         odt = out.dtype if out is not None else (out_dtype or (residual.dtype if residual is not None else x.dtype))
         mode = None
         if geglu and residual is None and odt == x.dtype:
@@ -861,7 +874,7 @@ def linear(x, w, bias=None, residual=None, out=None, out_dtype=None, geglu=False
             mode = LWS_F32
         elif not geglu and residual is None and odt == x.dtype:
             mode = LWS_16
-        if mode is not None and linear_ws_ok(rows, w.shape[0], K, mode, x):
+        if mode is not None and _lws_preferred(x, w, mode):
             return linear_ws(x, w, mode, bias=bias, residual=residual, out=out)
     return conv_gemm(x, w, w.shape[0], w_in=rows, bias=bias, residual=residual, out=out, out_dtype=out_dtype,
                      geglu=geglu, split_out=split_out, gn_stats=gn_stats)

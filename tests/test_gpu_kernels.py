@@ -399,6 +399,18 @@ def test_linear_geglu_epilogue(dtype, mnk):
     check("linear+geglu", got, want, TOL[dtype])
 
 
+def lws_planned(o, x, w, mode, k, chb, flat=None, **kw):
+    """Before a pf_linear_ws launch: the library's plan of it (ops.linear_ws(want_plan=True): nothing allocated, nothing launched) names
+    the k_linear_ws instantiation (k, chb, mode) -- and, where the test states it, the grid layout (flat / XCD-grouped)."""
+    g = o.linear_ws(x, w, mode, want_plan=True, **kw)
+    assert (g.supported, g.k, g.chb) == (1, k, chb), (g.supported, g.k, g.chb)
+    assert g.nblocks * chb == w.shape[0] and g.ntiles == -(-x.shape[0] // g.tile_tokens)
+    assert (g.splits_per_xcd > 0) != (g.flat_splits > 0)
+    if flat is not None:
+        assert (g.flat_splits > 0) == flat, (g.splits_per_xcd, g.flat_splits)
+    return g
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M", [64 * 37 + 40, 64, 64 * 300])
 def test_linear_ws_modes_vs_fp32(dtype, M):
@@ -411,9 +423,11 @@ def test_linear_ws_modes_vs_fp32(dtype, M):
         w, wf = q16(rnd(N, K, seed=seed) / K ** 0.5, dtype)
         b = rnd(N, seed=seed + 10)
         want = xf @ wf.T + b
+        lws_planned(o, x, w, o.LWS_16, 320, 320, flat=False)
         got = o.linear_ws(x, w, o.LWS_16, bias=b.to(DEV))
         check("linear_ws 16-bit N%d" % N, got, want, TOL[dtype])
         if N == 320:
+            lws_planned(o, x, w, o.LWS_F32, 320, 320)
             r = rnd(M, N, seed=70)
             got = o.linear_ws(x, w, o.LWS_F32, bias=b.to(DEV), residual=r.to(DEV))
             assert got.dtype == torch.float32
@@ -421,6 +435,7 @@ def test_linear_ws_modes_vs_fp32(dtype, M):
             check("linear_ws fp32, no bias / residual", o.linear_ws(x, w, o.LWS_F32), xf @ wf.T, 2e-5)
         if N == 2560:
             wi, bi = o.interleave_geglu(w, b.to(DEV))
+            lws_planned(o, x, wi, o.LWS_GEGLU, 320, 320)
             got = o.linear_ws(x, wi, o.LWS_GEGLU, bias=bi)
             assert got.shape == (M, N // 2)
             check("linear_ws geglu", got, want[:, :N // 2] * F.gelu(want[:, N // 2:]), TOL[dtype])
@@ -440,10 +455,12 @@ def test_linear_ws_k640_vs_fp32(dtype, M):
         b = rnd(N, seed=seed + 10)
         want = xf @ wf.T + b
         if N < 5120:
+            lws_planned(o, x, w, o.LWS_16, 640, 256, flat=False)
             check("linear_ws K640 16-bit N%d" % N, o.linear_ws(x, w, o.LWS_16, bias=b.to(DEV)), want, TOL[dtype])
             check("linear_ws K640 no bias N%d" % N, o.linear_ws(x, w, o.LWS_16), xf @ wf.T, TOL[dtype])
         else:
             wi, bi = o.interleave_geglu(w, b.to(DEV))
+            lws_planned(o, x, wi, o.LWS_GEGLU, 640, 256, flat=True)
             got = o.linear_ws(x, wi, o.LWS_GEGLU, bias=bi)
             assert got.shape == (M, N // 2)
             check("linear_ws K640 geglu", got, want[:, :N // 2] * F.gelu(want[:, N // 2:]), TOL[dtype])
@@ -456,6 +473,7 @@ def test_linear_ws_k640_vs_fp32(dtype, M):
     w, wf = q16(rnd(640, K, seed=170) / K ** 0.5, dtype)
     b = rnd(640, seed=171)
     want = xf @ wf.T + b
+    lws_planned(o, x, w, o.LWS_16, 640, 128, flat=False)
     got = o.linear_ws(x, w, o.LWS_16, bias=b.to(DEV))
     check("linear_ws K640 N640 16-bit", got, want, TOL[dtype])
     if o.linear_ws_ok(M, 640, K, o.LWS_16, x):
@@ -476,12 +494,14 @@ def test_linear_ws_k1280_vs_fp32(dtype, M):
         b = rnd(N, seed=seed + 10)
         want = xf @ wf.T + b
         if N < 10240:
+            lws_planned(o, x, w, o.LWS_16, 1280, 128, flat=N == 2560)          # (20 channel blocks: 160 of 256 CUs if grouped)
             got = o.linear_ws(x, w, o.LWS_16, bias=b.to(DEV))
             check("linear_ws K1280 16-bit N%d" % N, got, want, TOL[dtype])
             if o.linear_ws_ok(M, N, K, o.LWS_16, x):
                 assert torch.equal(o.linear(x, w, bias=b.to(DEV)), got)
         else:
             wi, bi = o.interleave_geglu(w, b.to(DEV))
+            assert lws_planned(o, x, wi, o.LWS_GEGLU, 1280, 128, flat=True).flat_splits == 3
             got = o.linear_ws(x, wi, o.LWS_GEGLU, bias=bi)
             assert got.shape == (M, N // 2)
             check("linear_ws K1280 geglu", got, want[:, :N // 2] * F.gelu(want[:, N // 2:]), TOL[dtype])
@@ -499,6 +519,7 @@ def test_linear_ws_transposed_output(dtype, n_batch, nk, N, K):
     x, xf = q16(rnd(M, K, seed=190), dtype)
     w, wf = q16(rnd(N, K, seed=191) / K ** 0.5, dtype)
     want = (xf @ wf.T).reshape(n_batch, nk, N).transpose(1, 2)
+    lws_planned(o, x, w, o.LWS_VT, K, 320 if K == 320 else 128, rows_per_batch=nk)
     vt = o.linear_ws(x, w, o.LWS_VT, rows_per_batch=nk)
     assert vt.shape == (n_batch, N, nk)
     check("linear_ws V^T", vt, want, TOL[dtype])
@@ -563,6 +584,7 @@ def test_linear_ws_with_layernorm_epilogue(dtype, M):
     b, r = rnd(N, seed=92), rnd(M, N, seed=93) + 30.0
     g, bt = 1.0 + 0.3 * rnd(N, seed=94), 0.2 * rnd(N, seed=95)
     want = xf @ wf.T + b + r
+    lws_planned(o, x, w, o.LWS_F32_LN, 320, 320, flat=False)
     out, ln = o.linear_ws(x, w, o.LWS_F32_LN, bias=b.to(DEV), residual=r.to(DEV), ln=(g.to(DEV), bt.to(DEV), 1e-5))
     assert out.dtype == torch.float32 and ln.dtype == dtype and ln.shape == (M, N)
     check("linear_ws fp32 + residual (LN mode)", out, want, 2e-5)
@@ -585,12 +607,13 @@ def test_linear_ws_qkv_with_transposed_values(dtype, n_batch, nk):
     x, xf = q16(rnd(M, K, seed=80), dtype)
     w, wf = q16(rnd(960, K, seed=81) / K ** 0.5, dtype)
     want = xf @ wf.T
+    lws_planned(o, x, w, o.LWS_QKV, 320, 320, flat=False, rows_per_batch=nk)
     qk, vt = o.linear_ws(x, w, o.LWS_QKV, rows_per_batch=nk)
     assert qk.shape == (M, 640) and vt.shape == (n_batch, 320, nk)
     check("qkv: q | k", qk, want[:, :640], TOL[dtype])
     check("qkv: V^T", vt, want[:, 640:].reshape(n_batch, nk, 320).transpose(1, 2), TOL[dtype])
     routed = o.linear_qkv(x, w, n_batch)
-    if M >= o.LINEAR_WS_MIN_ROWS:
+    if o.linear_ws_ok(M, 960, K, o.LWS_QKV, x):
         assert routed is not None and torch.equal(routed[0], qk) and torch.equal(routed[1], vt)
         r = rnd(M, 320, seed=82).to(DEV)
         a = o.linear(x, w[:320], residual=r)                      # fp32 residual stream in -> fp32 out (either kernel, by the row count)
