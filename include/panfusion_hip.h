@@ -694,8 +694,33 @@ typedef struct {
                                               * fixed order.  NULL: never split. */
 } pf_attn_bwd_desc;
 
-size_t pf_attention_bwd_workspace_size(const pf_attn_bwd_desc* desc);
+/* Layout rules (anything else is PF_ERR_ARG before any launch): every operand pointer, lse and delta non-NULL and 16-byte aligned; D 32 or
+ * 64; B, H, nq, nk > 0; q_ld, k_ld, v_ld, do_ld multiples of 8; qt_ld, kt_ld, dot_ld multiples of 4 that cover the token count; dq_ld,
+ * dk_ld, dv_ld multiples of 4; the row-major batch strides multiples of 8, the others of 4; bias and flags come together (with a bias:
+ * nk % 4 == 0, bias_ld % 4 == 0, bias_ld >= nk, flags_ld >= ceil(nk / 32)); every row-major leading dimension (q, k, v, do, dq, dk, dv)
+ * covers the H * D columns of a row; the planned grids are launchable (H and B at most 65535, grid x within HIP's limit); a non-NULL
+ * workspace holds the plan's workspace_bytes, 16-byte aligned.  The cover and the grid rule refuse only descriptors whose launch would
+ * read or write out of bounds or fail at launch. */
 pf_status pf_attention_bwd(const pf_attn_bwd_desc* desc, void* stream);
+/* Bytes of pf_attn_bwd_desc.workspace that let pf_attention_bwd split the query range of this problem (0: it would not split):
+ * workspace_bytes of the plan below; 0 for a bad descriptor. */
+size_t pf_attention_bwd_workspace_size(const pf_attn_bwd_desc* desc);
+/* The whole plan pf_attention_bwd resolves for a problem: the kernel pair, the split of the query range, the grids and the scratch. */
+typedef struct {
+    int kernel;          /* 0 k_attn_bwd_dq / _dkv<.., false> (whole 32-token tiles, no LDS), 1 the same <.., true> (guarded: ragged
+                          * token counts), 2 k_attn_bwd_dq_lds / k_attn_bwd_dkv_lds (LDS-staged) */
+    int qsplit;          /* blocks per key block that share the query range of the dkv launch (1: not split); > 1 adds the
+                          * k_attn_bwd_reduce launch */
+    int threads;         /* 256 */
+    unsigned dq_grid_x, dq_grid_y, dq_grid_z;
+    unsigned dkv_grid_x, dkv_grid_y, dkv_grid_z;
+    unsigned reduce_grid_x, reduce_grid_y, reduce_grid_z;   /* 0 when qsplit == 1 */
+    size_t workspace_bytes;   /* scratch of exactly this plan, 0 when qsplit == 1 */
+} pf_attn_bwd_plan;
+/* Looks only at the scalar members of desc (nothing is dereferenced, no GPU is needed), validates nothing else and reports the plan of a
+ * launch that hands over the workspace it asks for (a launch with a NULL workspace runs the same plan unsplit).  PF_ERR_ARG for a NULL
+ * pointer, non-positive B, H, nq or nk, or a head dim other than 32 or 64. */
+pf_status pf_attention_bwd_plan(const pf_attn_bwd_desc* desc, pf_attn_bwd_plan* out);
 
 /* LayerNorm backward (rows of width C <= 2048, C % 8 == 0).  x (+ pe, as pf_layernorm) is the forward input, dy fp32
  * [rows][C] the gradient of the normalised output, dres (optional fp32 [rows][C]) a gradient that by-passes the norm:

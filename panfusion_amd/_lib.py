@@ -107,6 +107,17 @@ class AttnBwdDesc(C.Structure):
     ]
 
 
+class AttnBwdPlan(C.Structure):
+    """pf_attn_bwd_plan"""
+    _fields_ = [
+        ("kernel", c_int), ("qsplit", c_int), ("threads", c_int),
+        ("dq_grid_x", C.c_uint), ("dq_grid_y", C.c_uint), ("dq_grid_z", C.c_uint),
+        ("dkv_grid_x", C.c_uint), ("dkv_grid_y", C.c_uint), ("dkv_grid_z", C.c_uint),
+        ("reduce_grid_x", C.c_uint), ("reduce_grid_y", C.c_uint), ("reduce_grid_z", C.c_uint),
+        ("workspace_bytes", c_size_t),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/panfusion_hip.h declares
 SIGNATURES = {
     "pf_version": (c_int, []),
@@ -199,6 +210,7 @@ SIGNATURES = {
     "pf_attention_delta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_int, c_long, c_void_p, c_void_p]),
     "pf_attention_bwd": (c_int, [C.POINTER(AttnBwdDesc), c_void_p]),
     "pf_attention_bwd_workspace_size": (c_size_t, [C.POINTER(AttnBwdDesc)]),
+    "pf_attention_bwd_plan": (c_int, [C.POINTER(AttnBwdDesc), C.POINTER(AttnBwdPlan)]),
     "pf_layernorm_bwd_parts": (c_int, [c_long]),
     "pf_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_int, c_void_p, c_float, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),

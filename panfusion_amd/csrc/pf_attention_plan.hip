@@ -1,6 +1,7 @@
 // Host side of the attention front ends (no device code): the environment knobs, the descriptor checks pf_attention and
 // pf_attention_wide share, and THE plan of a pf_attention problem -- which kernel and instantiation, the split of the key range, grid
-// and scratch -- that pf_attention launches and pf_attention_plan / pf_attention_workspace_size report.
+// and scratch -- that pf_attention launches and pf_attention_plan / pf_attention_workspace_size report.  The same for pf_attention_bwd
+// (kernels in pf_backward.hip): its knobs, its descriptor checks and THE plan behind pf_attention_bwd_plan / _workspace_size.
 #include "pf_attention_plan.h"
 #include <algorithm>
 
@@ -110,6 +111,74 @@ pf_attn_plan plan_attention_launch(const pf_attn_desc* d) {
     return g.splits > 1 && !scratch ? plan_attention(d, false) : g;
 }
 
+// ---- pf_attention_bwd -----------------------------------------------------------------------------------------------------------------
+
+const AttnBwdTuning& attn_bwd_tuning() {
+    static const AttnBwdTuning t;
+    return t;
+}
+
+// Query split of the keys-stationary launch: towards ~512 blocks, at least 8 query tiles (256 queries) per block.  A launch with few
+// blocks (the 128 text keys of a cross-attention: H x B blocks walking all queries; one panorama sample) splits the query range over
+// several blocks per key block, which leave fp32 partial sums [qsplit][B][nk][H * D] for dK and for dV, added in a fixed order by
+// k_attn_bwd_reduce.  (That kernel works on quads of the H * D columns: whole for D in {32, 64}.)
+static int plan_qsplit(const pf_attn_bwd_desc* d) {
+    const long base = cdiv(d->nk, 128) * d->H * d->B;
+    if (base >= 384) return 1;
+    return static_cast<int>(std::max<long>(1, std::min<long>(cdiv(512, base), (d->nq / 32) / 8)));
+}
+
+pf_attn_bwd_plan plan_attention_bwd(const pf_attn_bwd_desc* d, bool allow_split) {
+    const AttnBwdTuning& t = attn_bwd_tuning();
+    pf_attn_bwd_plan g{};
+    g.threads = 256; g.qsplit = 1;
+    const bool tail = d->nq % 32 != 0 || d->nk % 32 != 0;          // ragged token counts: guarded loads, masked tails
+    // LDS-staged kernels: whole 32-token tiles, 16-byte rows for the cooperative loads of the transposed tiles
+    const bool rows16 = d->qt_ld % 8 == 0 && d->kt_ld % 8 == 0 && d->dot_ld % 8 == 0 && d->qt_bs % 8 == 0 && d->kt_bs % 8 == 0 && d->dot_bs % 8 == 0;
+    g.kernel = t.lds && !tail && rows16 ? 2 : tail ? 1 : 0;
+    if (g.kernel == 2 && t.qsplit && allow_split) g.qsplit = plan_qsplit(d);
+    g.dq_grid_x = static_cast<unsigned>(cdiv(d->nq, 128)); g.dq_grid_y = d->H; g.dq_grid_z = d->B;
+    g.dkv_grid_x = static_cast<unsigned>(cdiv(d->nk, 128) * g.qsplit); g.dkv_grid_y = d->H; g.dkv_grid_z = d->B;
+    if (g.qsplit > 1) {
+        const size_t elems = static_cast<size_t>(d->B) * d->nk * d->H * d->D;
+        g.reduce_grid_x = static_cast<unsigned>(cdiv(static_cast<long>(elems / 4), 256)); g.reduce_grid_y = g.reduce_grid_z = 1;
+        g.workspace_bytes = 2 * g.qsplit * elems * sizeof(float);
+    }
+    return g;
+}
+
+bool attn_bwd_grids_launchable(const pf_attn_bwd_plan& g) {
+    const unsigned lim = 0xFFFFFFFFu / g.threads;                 // HIP refuses grid x block sizes past 2^32 - 1 threads
+    auto ok = [lim](unsigned x, unsigned y, unsigned z) { return x <= lim && y <= 65535 && z <= 65535; };
+    return ok(g.dq_grid_x, g.dq_grid_y, g.dq_grid_z) && ok(g.dkv_grid_x, g.dkv_grid_y, g.dkv_grid_z) && ok(g.reduce_grid_x, g.reduce_grid_y, g.reduce_grid_z);
+}
+
+pf_status validate_attn_bwd_desc(const pf_attn_bwd_desc* d, const char* who) {
+    PF_REQUIRE(d, "%s: null descriptor", who);
+    PF_REQUIRE(d->q && d->k && d->v && d->dout && d->qt && d->kt && d->dot && d->dq && d->dk && d->dv && d->lse && d->delta, "%s: null pointer", who);
+    PF_REQUIRE(d->D == 32 || d->D == 64, "%s: head dim %d unsupported (32 or 64)", who, d->D);
+    PF_REQUIRE(d->B > 0 && d->H > 0 && d->nq > 0 && d->nk > 0, "%s: bad sizes", who);
+    PF_REQUIRE(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->v_ld % 8 == 0 && d->do_ld % 8 == 0, "%s: row-major leading dimensions must be multiples of 8", who);
+    PF_REQUIRE(d->qt_ld % 4 == 0 && d->kt_ld % 4 == 0 && d->dot_ld % 4 == 0 && d->qt_ld >= d->nq && d->dot_ld >= d->nq && d->kt_ld >= d->nk,
+               "%s: transposed leading dimensions must be multiples of 4 and cover the token count", who);
+    PF_REQUIRE(d->dq_ld % 4 == 0 && d->dk_ld % 4 == 0 && d->dv_ld % 4 == 0, "%s: output leading dimensions must be multiples of 4", who);
+    PF_REQUIRE(d->q_bs % 8 == 0 && d->k_bs % 8 == 0 && d->v_bs % 8 == 0 && d->do_bs % 8 == 0 && d->qt_bs % 4 == 0 && d->kt_bs % 4 == 0 &&
+               d->dot_bs % 4 == 0 && d->dq_bs % 4 == 0 && d->dk_bs % 4 == 0 && d->dv_bs % 4 == 0, "%s: batch strides misaligned", who);
+    PF_REQUIRE(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->dout) && aligned16(d->qt) && aligned16(d->kt) &&
+               aligned16(d->dot) && aligned16(d->dq) && aligned16(d->dk) && aligned16(d->dv) && aligned16(d->lse) && aligned16(d->delta),
+               "%s: pointers must be 16-byte aligned", who);
+    PF_REQUIRE((d->bias == nullptr) == (d->flags == nullptr), "%s: bias and flags come together", who);
+    if (d->bias) {
+        PF_REQUIRE(d->nk % 4 == 0 && d->bias_ld % 4 == 0 && d->bias_ld >= d->nk && aligned16(d->bias), "%s: bias needs nk %% 4 == 0 and an aligned ld >= nk", who);
+        PF_REQUIRE(d->flags_ld >= (d->nk + 31) / 32, "%s: flags_ld too small", who);
+    }
+    const long cols = static_cast<long>(d->H) * d->D;
+    PF_REQUIRE(d->q_ld >= cols && d->k_ld >= cols && d->v_ld >= cols && d->do_ld >= cols && d->dq_ld >= cols && d->dk_ld >= cols && d->dv_ld >= cols,
+               "%s: q_ld, k_ld, v_ld, do_ld, dq_ld, dk_ld and dv_ld must cover H * D = %ld columns", who, cols);
+    PF_REQUIRE(attn_bwd_grids_launchable(plan_attention_bwd(d, true)), "%s: B=%d, H=%d, nq=%d, nk=%d exceed the grid limits of the launch", who, d->B, d->H, d->nq, d->nk);
+    return PF_OK;
+}
+
 }  // namespace pf
 
 using namespace pf;
@@ -125,4 +194,17 @@ extern "C" pf_status pf_attention_plan(const pf_attn_desc* d, pf_attn_plan* out)
 extern "C" size_t pf_attention_workspace_size(const pf_attn_desc* d) {
     pf_attn_plan g;
     return pf_attention_plan(d, &g) == PF_OK ? g.workspace_bytes : 0;
+}
+
+extern "C" pf_status pf_attention_bwd_plan(const pf_attn_bwd_desc* d, pf_attn_bwd_plan* out) {
+    PF_REQUIRE(d && out, "pf_attention_bwd_plan: null pointer");
+    PF_REQUIRE(d->B > 0 && d->H > 0 && d->nq > 0 && d->nk > 0, "pf_attention_bwd_plan: bad sizes");
+    PF_REQUIRE(d->D == 32 || d->D == 64, "pf_attention_bwd_plan: head dim %d unsupported (32 or 64)", d->D);
+    *out = plan_attention_bwd(d, true);
+    return PF_OK;
+}
+
+extern "C" size_t pf_attention_bwd_workspace_size(const pf_attn_bwd_desc* d) {
+    pf_attn_bwd_plan g;
+    return pf_attention_bwd_plan(d, &g) == PF_OK ? g.workspace_bytes : 0;
 }

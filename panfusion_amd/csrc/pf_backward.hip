@@ -9,9 +9,12 @@
 //                        both use the transposed-product layout of the forward kernel (pf_attention.hip): the owner
 //                        index is the MFMA column = the lane, so per-owner scalars (lse, delta) are lane scalars in the
 //                        first kernel and the probabilities feed the second product straight from the registers.
+//                        Each direction has one tile step (attn_bwd_dq_step, attn_bwd_dkv_step) shared by its direct and its
+//                        LDS-staged kernel (the guarded tile of k_attn_bwd_dkv alone keeps its own body, see there); which pair
+//                        runs is the plan's decision (pf_attention_plan.hip).
 //   LayerNorm backward   one row per wavefront, per-block partial sums for gamma / beta (reduced by k_colsum)
 //   GEGLU backward, column sums (bias gradients), gradient normalisation (amax -> power-of-two scale).
-#include "pf_common.h"
+#include "pf_attention_plan.h"
 #include <algorithm>
 #include <stdlib.h>
 #include <type_traits>
@@ -61,6 +64,213 @@ __device__ __forceinline__ u16x8 load_t_frag_guard(const unsigned short* row, in
     return v;
 }
 
+// LDS tiles of the staged kernels: row-major [32][D] with rows padded to D + 8 elements (fragment reads: 16 bytes per lane, rows 144 /
+// 80 bytes apart), transposed [D][32] with rows padded to 36 elements (two 8-byte reads per lane, rows 72 bytes apart)
+template <int D> struct BwdTile {
+    static constexpr int RS = D + 8, TS = 32 + 4;
+    static constexpr int ROWMAJ = 32 * RS, TRANS = D * TS;
+    static constexpr int CH_R = 32 * (D / 8), CH_T = D * 4;      // 16-byte chunks per row-major / transposed tile
+};
+
+__device__ __forceinline__ u16x8 lds_t_frag(const unsigned short* row, int s2, int hi) {
+    const unsigned short* pp = row + 16 * s2 + 4 * hi;
+    const u16x4 lo = *reinterpret_cast<const u16x4*>(pp);
+    const u16x4 up = *reinterpret_cast<const u16x4*>(pp + 8);
+    return u16x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+}
+
+// ---- the walked side -----------------------------------------------------------------------------------------------------------
+// A wavefront owns 32 tokens of one side (queries for dQ, keys for dK / dV) and walks past the OTHER side in tiles of 32 tokens: two
+// row-major operands (dq: K, V; dkv: Q, dO) at the head's first column and their transposes (dq: K^T; dkv: Q^T, dO^T) at the head's
+// first channel row.
+struct BwdWalked {
+    const unsigned short* rp[2]; int r_ld[2];
+    const unsigned short* tp[2]; int t_ld[2];
+};
+
+// The two forms of a direction differ only in where the fragments of a walked tile come from.  A fragment source hands the shared steps
+//   row(i, ks)         the 16 bytes of row-major operand i at token `lane % 32` of the tile, channels 16 ks + 8 hi ...
+//   trans(i, d, s2)    the fragment of transposed operand i at channel row 32 d + lane % 32, tokens in load_t_frag order
+//   stats(g, lv, dv)   lse and delta of the tile's tokens 8 g + 4 hi ... + 3 (dkv only: the walked side are the queries; whole tiles)
+// Global memory: fragment-shaped loads from every wave; TAIL = ragged token counts (rows clamped, tokens >= n_tok read as zero).
+template <bool TAIL> struct GlobalFrags {
+    BwdWalked w;
+    int n_tok, l32, hi;                          // the token count of the walked side, lane % 32, lane / 32
+    const float *lsep, *delp;                    // dkv: lse / delta of the (batch, head)
+    int t0;                                      // the tile's first token
+    __device__ __forceinline__ u16x8 row(int i, int ks) const {
+        const int tok = TAIL ? min(t0 + l32, n_tok - 1) : t0 + l32;
+        return *reinterpret_cast<const u16x8*>(w.rp[i] + static_cast<long>(tok) * w.r_ld[i] + 16 * ks + 8 * hi);
+    }
+    __device__ __forceinline__ u16x8 trans(int i, int d, int s2) const {
+        const unsigned short* r = w.tp[i] + static_cast<long>(d * 32 + l32) * w.t_ld[i];
+        return TAIL ? load_t_frag_guard(r, t0, s2, hi, n_tok) : load_t_frag(r, t0, s2, hi);
+    }
+    __device__ __forceinline__ void stats(int g, float (&lv)[4], float (&dv)[4]) const {      // (whole tiles: the guarded dkv tile is not a step)
+        const float4 l4 = *reinterpret_cast<const float4*>(lsep + t0 + 8 * g + 4 * hi);
+        const float4 d4 = *reinterpret_cast<const float4*>(delp + t0 + 8 * g + 4 * hi);
+        lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+        dv[0] = d4.x; dv[1] = d4.y; dv[2] = d4.z; dv[3] = d4.w;
+    }
+};
+
+// LDS: one staged buffer (the two row-major tiles, then the transposed ones; BwdStage below), lse | delta of its 32 queries in lsd[64].
+template <int D> struct LdsFrags {
+    typedef BwdTile<D> TL;
+    const unsigned short* buf; const float* lsd;
+    int l32, hi;
+    __device__ __forceinline__ u16x8 row(int i, int ks) const {
+        return *reinterpret_cast<const u16x8*>(buf + i * TL::ROWMAJ + l32 * TL::RS + 16 * ks + 8 * hi);
+    }
+    __device__ __forceinline__ u16x8 trans(int i, int d, int s2) const {
+        return lds_t_frag(buf + 2 * TL::ROWMAJ + i * TL::TRANS + (d * 32 + l32) * TL::TS, s2, hi);
+    }
+    __device__ __forceinline__ void stats(int g, float (&lv)[4], float (&dv)[4]) const {
+        const float4 l4 = *reinterpret_cast<const float4*>(lsd + 8 * g + 4 * hi);
+        const float4 d4 = *reinterpret_cast<const float4*>(lsd + 32 + 8 * g + 4 * hi);
+        lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+        dv[0] = d4.x; dv[1] = d4.y; dv[2] = d4.z; dv[3] = d4.w;
+    }
+};
+
+// Staging of a walked tile for the LDS forms, by the 256 threads of a block: coalesced 16-byte global loads into registers (load), then
+// into one LDS buffer (store) -- double buffered by the kernels, the next tile's loads in flight during the MFMAs, one barrier per tile.
+// The direct kernels issue fragment-shaped loads (32 cache lines per instruction) from every wave instead.  NT transposed operands.
+// Chunk ownership: row-major chunk c -> (row c / (D/8), 8 channels at (c % (D/8)) * 8); transposed chunk c -> (row c / 4, 8 tokens at (c % 4) * 8).
+template <int D, int NT> struct BwdStage {
+    typedef BwdTile<D> TL;
+    static constexpr int NR = (TL::CH_R + 255) / 256, NC = (TL::CH_T + 255) / 256;
+    static constexpr int BUF = 2 * TL::ROWMAJ + NT * TL::TRANS;
+    u16x8 r[2][NR], tr[NT][NC];
+    __device__ __forceinline__ void load(const BwdWalked& w, int t0, int t) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int c = t + 256 * i;
+            if (c < TL::CH_R) {
+                const int row = c / (D / 8), ch = (c % (D / 8)) * 8;
+#pragma unroll
+                for (int o = 0; o < 2; ++o) r[o][i] = *reinterpret_cast<const u16x8*>(w.rp[o] + static_cast<long>(t0 + row) * w.r_ld[o] + ch);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c = t + 256 * i;
+            if (c < TL::CH_T) {
+#pragma unroll
+                for (int o = 0; o < NT; ++o) tr[o][i] = *reinterpret_cast<const u16x8*>(w.tp[o] + static_cast<long>(c >> 2) * w.t_ld[o] + t0 + (c & 3) * 8);
+            }
+        }
+    }
+    __device__ __forceinline__ void store(unsigned short* buf, int t) const {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int c = t + 256 * i;
+            if (c < TL::CH_R) {
+                const int off = (c / (D / 8)) * TL::RS + (c % (D / 8)) * 8;
+#pragma unroll
+                for (int o = 0; o < 2; ++o) *reinterpret_cast<u16x8*>(buf + o * TL::ROWMAJ + off) = r[o][i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c = t + 256 * i;
+            if (c < TL::CH_T) {
+                const int off = (c >> 2) * TL::TS + (c & 3) * 8;          // 8-byte aligned (72-byte rows)
+#pragma unroll
+                for (int o = 0; o < NT; ++o) {
+                    unsigned short* dst = buf + 2 * TL::ROWMAJ + o * TL::TRANS + off;
+                    const u16x8 a = tr[o][i];
+                    *reinterpret_cast<u16x4*>(dst) = u16x4{a[0], a[1], a[2], a[3]};
+                    *reinterpret_cast<u16x4*>(dst + 4) = u16x4{a[4], a[5], a[6], a[7]};
+                }
+            }
+        }
+    }
+};
+
+// ---- pieces both directions share --------------------------------------------------------------------------------------------------
+// the owner's fragments: its row of two row-major operands (dq: Q, dO; dkv: K, V), kept in registers for the whole walk
+template <typename T, int D>
+__device__ __forceinline__ void bwd_owner_frags(const unsigned short* a, const unsigned short* b, int hi, typename Mfma32<T>::frag (&fa)[D / 16],
+                                                typename Mfma32<T>::frag (&fb)[D / 16]) {
+    typedef typename Mfma32<T>::frag frag;
+#pragma unroll
+    for (int s = 0; s < D / 16; ++s) {
+        fa[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(a + 16 * s + 8 * hi));
+        fb[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(b + 16 * s + 8 * hi));
+    }
+}
+
+template <int DB> __device__ __forceinline__ void bwd_zero(f32x16 (&acc)[DB]) {
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[d][r] = 0.f;
+}
+
+// the owner's row of a transposed accumulator, in the 16-bit type
+template <typename T, int D, bool SCALED>
+__device__ __forceinline__ void bwd_store16(unsigned short* op, const f32x16 (&acc)[D / 32], float scale, int hi) {
+#pragma unroll
+    for (int d = 0; d < D / 32; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            u16x4 w;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] = from_f32<T>(SCALED ? acc[d][4 * g + e] * scale : acc[d][4 * g + e]);
+            *reinterpret_cast<u16x4*>(op + d * 32 + 8 * g + 4 * hi) = w;
+        }
+}
+
+// ---- queries-stationary: dQ ------------------------------------------------------------------------------------------------------
+// One key tile: S^T = K Q^T and dP^T = V dO^T ([key][query]: the lane's column is its query), the bias of a flagged tile,
+// dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T.  flag: the tile's flag byte (NULL: no bias table); bias_row: the lane's row of the bias table.
+// (The sources are a few words: passed by value, which is also what keeps the register counts of the kernels where they were.)
+template <typename T, int D, bool TAIL, typename Src>
+__device__ __forceinline__ void attn_bwd_dq_step(const Src src, const typename Mfma32<T>::frag (&qf)[D / 16], const typename Mfma32<T>::frag (&dof)[D / 16],
+                                                 float lse, float delta, float c2, const uint8_t* flag, const float* bias_row, int k0, int nk, int hi,
+                                                 f32x16 (&acc)[D / 32]) {
+    typedef typename Mfma32<T>::frag frag;
+    f32x16 s, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < D / 16; ++ks) {
+        const u16x8 kf = src.row(0, ks);
+        const u16x8 vf = src.row(1, ks);
+        s = Mfma32<T>::run(__builtin_bit_cast(frag, kf), qf[ks], s);          // S^T  [key][query]
+        dp = Mfma32<T>::run(__builtin_bit_cast(frag, vf), dof[ks], dp);       // dP^T [key][query]
+    }
+    float sv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
+    if (flag && *flag) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (TAIL && k0 + 8 * g + 4 * hi + 3 >= nk) continue;      // (nk % 4 == 0 with a bias: whole quads)
+            const float4 bv = *reinterpret_cast<const float4*>(bias_row + k0 + 8 * g + 4 * hi);
+            sv[4 * g + 0] += bv.x * LOG2E;
+            sv[4 * g + 1] += bv.y * LOG2E;
+            sv[4 * g + 2] += bv.z * LOG2E;
+            sv[4 * g + 3] += bv.w * LOG2E;
+        }
+    }
+    u16x8 pb[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float pr = exp2f(sv[r] - lse);
+        if (TAIL && k0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= nk) pr = 0.f;
+        pb[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - delta));
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int d = 0; d < D / 32; ++d) {
+            const u16x8 a = src.trans(0, d, s2);
+            acc[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, pb[s2]), acc[d]);   // dQ^T += K^T dS^T
+        }
+}
+
 template <typename T, int D, bool TAIL>
 __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnBwdParams p) {
     constexpr int KS = D / 16, DB = D / 32;
@@ -74,83 +284,128 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnBwdParams p) {
     const int qrow = TAIL ? min(q0 + ql, p.nq - 1) : q0 + ql;
     const unsigned short* qp = p.q + b * p.q_bs + static_cast<long>(qrow) * p.q_ld + h * D;
     const unsigned short* dop = p.dout + b * p.do_bs + static_cast<long>(qrow) * p.do_ld + h * D;
-    const unsigned short* kp = p.k + b * p.k_bs + h * D;
-    const unsigned short* vp = p.v + b * p.v_bs + h * D;
-    const unsigned short* ktp = p.kt + b * p.kt_bs + static_cast<long>(h) * D * p.kt_ld;
-
+    const BwdWalked w{{p.k + b * p.k_bs + h * D, p.v + b * p.v_bs + h * D}, {p.k_ld, p.v_ld}, {p.kt + b * p.kt_bs + static_cast<long>(h) * D * p.kt_ld, nullptr}, {p.kt_ld, 0}};      // K, V | K^T
     frag qf[KS], dof[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        qf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(qp + 16 * s + 8 * hi));
-        dof[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(dop + 16 * s + 8 * hi));
-    }
+    bwd_owner_frags<T, D>(qp, dop, hi, qf, dof);
     const long stat = (b * p.H + h) * p.nq + qrow;
     const float lse = p.lse[stat], delta = p.delta[stat];
-    const float c2 = p.scale_log2e;
-
     f32x16 acc[DB];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[d][r] = 0.f;
+    bwd_zero(acc);
 
     const uint8_t* flag_row = p.flags ? p.flags + static_cast<long>(q0 >> 5) * p.flags_ld : nullptr;
     const float* bias_row = p.bias ? p.bias + static_cast<long>(qrow) * p.bias_ld : nullptr;
     const int nkt = (p.nk + 31) / 32;
     for (int kt = 0; kt < nkt; ++kt) {
-        const int k0 = kt * 32;
-        const int krow = TAIL ? min(k0 + ql, p.nk - 1) : k0 + ql;
-        f32x16 s, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u16x8 kf = *reinterpret_cast<const u16x8*>(kp + static_cast<long>(krow) * p.k_ld + 16 * ks + 8 * hi);
-            const u16x8 vf = *reinterpret_cast<const u16x8*>(vp + static_cast<long>(krow) * p.v_ld + 16 * ks + 8 * hi);
-            s = Mfma32<T>::run(__builtin_bit_cast(frag, kf), qf[ks], s);          // S^T  [key][query]
-            dp = Mfma32<T>::run(__builtin_bit_cast(frag, vf), dof[ks], dp);       // dP^T [key][query]
-        }
-        float sv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
-        if (flag_row && flag_row[kt]) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (TAIL && k0 + 8 * g + 4 * hi + 3 >= p.nk) continue;      // (nk % 4 == 0 with a bias: whole quads)
-                const float4 bv = *reinterpret_cast<const float4*>(bias_row + k0 + 8 * g + 4 * hi);
-                sv[4 * g + 0] += bv.x * LOG2E;
-                sv[4 * g + 1] += bv.y * LOG2E;
-                sv[4 * g + 2] += bv.z * LOG2E;
-                sv[4 * g + 3] += bv.w * LOG2E;
-            }
-        }
-        u16x8 pb[2];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float pr = exp2f(sv[r] - lse);
-            if (TAIL && k0 + (r & 3) + 8 * (r >> 2) + 4 * hi >= p.nk) pr = 0.f;
-            pb[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - delta));
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                const unsigned short* trow = ktp + static_cast<long>(d * 32 + ql) * p.kt_ld;
-                const u16x8 a = TAIL ? load_t_frag_guard(trow, k0, s2, hi, p.nk) : load_t_frag(trow, k0, s2, hi);
-                acc[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, pb[s2]), acc[d]);   // dQ^T += K^T dS^T
-            }
+        const GlobalFrags<TAIL> src{w, p.nk, ql, hi, nullptr, nullptr, kt * 32};
+        attn_bwd_dq_step<T, D, TAIL>(src, qf, dof, lse, delta, p.scale_log2e, flag_row ? flag_row + kt : nullptr, bias_row, kt * 32, p.nk, hi, acc);
     }
     if (TAIL && q0 + ql >= p.nq) return;
-    unsigned short* op = p.dq + b * p.dq_bs + static_cast<long>(q0 + ql) * p.dq_ld + h * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            u16x4 w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = from_f32<T>(acc[d][4 * g + e] * p.scale);
-            *reinterpret_cast<u16x4*>(op + d * 32 + 8 * g + 4 * hi) = w;
+    bwd_store16<T, D, true>(p.dq + b * p.dq_bs + static_cast<long>(q0 + ql) * p.dq_ld + h * D, acc, p.scale, hi);
+}
+
+// LDS-staged form (token counts that are multiples of 32): same math and register layout, the key tile staged once per block (K, V, K^T)
+template <typename T, int D>
+__global__ __launch_bounds__(256) void k_attn_bwd_dq_lds(const AttnBwdParams p) {
+    constexpr int KS = D / 16, DB = D / 32;
+    typedef BwdStage<D, 1> Stage;
+    typedef typename Mfma32<T>::frag frag;
+    __shared__ __attribute__((aligned(16))) unsigned short smem[2 * Stage::BUF];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ql = lane & 31, hi = lane >> 5;
+    const int q0 = (blockIdx.x * 4 + wave) * 32;
+    const bool live = q0 < p.nq;                                   // (a block's trailing waves still help staging)
+    const int h = blockIdx.y;
+    const long b = blockIdx.z;
+    const int qrow = live ? q0 + ql : p.nq - 1;
+    const unsigned short* qp = p.q + b * p.q_bs + static_cast<long>(qrow) * p.q_ld + h * D;
+    const unsigned short* dop = p.dout + b * p.do_bs + static_cast<long>(qrow) * p.do_ld + h * D;
+    const BwdWalked w{{p.k + b * p.k_bs + h * D, p.v + b * p.v_bs + h * D}, {p.k_ld, p.v_ld}, {p.kt + b * p.kt_bs + static_cast<long>(h) * D * p.kt_ld, nullptr}, {p.kt_ld, 0}};      // K, V | K^T
+    frag qf[KS], dof[KS];
+    bwd_owner_frags<T, D>(qp, dop, hi, qf, dof);
+    const long stat = (b * p.H + h) * p.nq + qrow;
+    const float lse = p.lse[stat], delta = p.delta[stat];
+    f32x16 acc[DB];
+    bwd_zero(acc);
+
+    Stage stage;
+    const uint8_t* flag_row = p.flags ? p.flags + static_cast<long>(min(q0, p.nq - 32) >> 5) * p.flags_ld : nullptr;
+    const float* bias_row = p.bias ? p.bias + static_cast<long>(qrow) * p.bias_ld : nullptr;
+    const int nkt = p.nk / 32;
+    stage.load(w, 0, t);
+    stage.store(smem, t);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        if (kt + 1 < nkt) stage.load(w, (kt + 1) * 32, t);
+        if (live) {
+            const LdsFrags<D> src{smem + (kt & 1) * Stage::BUF, nullptr, ql, hi};
+            attn_bwd_dq_step<T, D, false>(src, qf, dof, lse, delta, p.scale_log2e, flag_row ? flag_row + kt : nullptr, bias_row, kt * 32, p.nk, hi, acc);
         }
+        if (kt + 1 < nkt) stage.store(smem + ((kt + 1) & 1) * Stage::BUF, t);      // that buffer was last read in step kt - 1: every wave passed the barrier since
+        __syncthreads();
+    }
+    if (!live) return;
+    bwd_store16<T, D, true>(p.dq + b * p.dq_bs + static_cast<long>(q0 + ql) * p.dq_ld + h * D, acc, p.scale, hi);
+}
+
+// ---- keys-stationary: dK, dV --------------------------------------------------------------------------------------------------------
+// One query tile: S = Q K^T and dP = dO V^T ([query][key]: register r <-> query q0 + (r & 3) + 8 (r >> 2) + 4 hi, the lane's column is
+// its key), the bias of a flagged tile (flags[tile]), P and dS = P o (dP - delta), dV^T += dO^T P, dK^T += Q^T dS.  key: the lane's key.
+// Whole tiles only: ragged token counts run the guarded tile inside k_attn_bwd_dkv.
+template <typename T, int D, typename Src>
+__device__ __forceinline__ void attn_bwd_dkv_step(const Src src, const typename Mfma32<T>::frag (&kf)[D / 16], const typename Mfma32<T>::frag (&vf)[D / 16],
+                                                  float c2, const uint8_t* flags, long tile, const float* bias, long bias_ld, int q0, int key, int hi,
+                                                  f32x16 (&acc_k)[D / 32], f32x16 (&acc_v)[D / 32]) {
+    typedef typename Mfma32<T>::frag frag;
+    f32x16 s, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < D / 16; ++ks) {
+        const u16x8 qf = src.row(0, ks);
+        const u16x8 df = src.row(1, ks);
+        s = Mfma32<T>::run(__builtin_bit_cast(frag, qf), kf[ks], s);           // S  [query][key]
+        dp = Mfma32<T>::run(__builtin_bit_cast(frag, df), vf[ks], dp);         // dP [query][key]
+    }
+    float sv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
+    if (flags && flags[tile]) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            sv[r] += bias[static_cast<long>(qi) * bias_ld + key] * LOG2E;
+        }
+    }
+    u16x8 pp[2], pd[2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float lv[4], dv[4];
+        src.stats(g, lv, dv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            const float pr = exp2f(sv[r] - lv[e]);
+            pp[r >> 3][r & 7] = from_f32<T>(pr);
+            pd[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - dv[e]));
+        }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int d = 0; d < D / 32; ++d) {
+            const u16x8 a_do = src.trans(1, d, s2);
+            const u16x8 a_q = src.trans(0, d, s2);
+            acc_v[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_do), __builtin_bit_cast(frag, pp[s2]), acc_v[d]);   // dV^T += dO^T P
+            acc_k[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_q), __builtin_bit_cast(frag, pd[s2]), acc_k[d]);    // dK^T += Q^T dS
+        }
+}
+
+// the owner's rows of dK (scaled) and dV, in the 16-bit type
+template <typename T, int D>
+__device__ __forceinline__ void attn_bwd_dkv_store16(const AttnBwdParams& p, long b, int h, int key, int hi, const f32x16 (&acc_k)[D / 32],
+                                                     const f32x16 (&acc_v)[D / 32]) {
+    bwd_store16<T, D, true>(p.dk + b * p.dk_bs + static_cast<long>(key) * p.dk_ld + h * D, acc_k, p.scale, hi);
+    bwd_store16<T, D, false>(p.dv + b * p.dv_bs + static_cast<long>(key) * p.dv_ld + h * D, acc_v, 1.f, hi);
 }
 
 template <typename T, int D, bool TAIL>
@@ -166,136 +421,91 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(const AttnBwdParams p) {
     const int krow = TAIL ? min(k0 + kl, p.nk - 1) : k0 + kl;
     const unsigned short* kp = p.k + b * p.k_bs + static_cast<long>(krow) * p.k_ld + h * D;
     const unsigned short* vp = p.v + b * p.v_bs + static_cast<long>(krow) * p.v_ld + h * D;
-    const unsigned short* qp = p.q + b * p.q_bs + h * D;
-    const unsigned short* dop = p.dout + b * p.do_bs + h * D;
-    const unsigned short* qtp = p.qt + b * p.qt_bs + static_cast<long>(h) * D * p.qt_ld;
-    const unsigned short* dotp = p.dot + b * p.dot_bs + static_cast<long>(h) * D * p.dot_ld;
-
+    const BwdWalked w{{p.q + b * p.q_bs + h * D, p.dout + b * p.do_bs + h * D}, {p.q_ld, p.do_ld},
+                      {p.qt + b * p.qt_bs + static_cast<long>(h) * D * p.qt_ld, p.dot + b * p.dot_bs + static_cast<long>(h) * D * p.dot_ld}, {p.qt_ld, p.dot_ld}};      // Q, dO | Q^T, dO^T
     frag kf[KS], vf[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        kf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(kp + 16 * s + 8 * hi));
-        vf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(vp + 16 * s + 8 * hi));
-    }
-    const float c2 = p.scale_log2e;
+    bwd_owner_frags<T, D>(kp, vp, hi, kf, vf);
+    f32x16 acc_k[DB], acc_v[DB];
+    bwd_zero(acc_k);
+    bwd_zero(acc_v);
+
     const float* lsep = p.lse + (b * p.H + h) * p.nq;
     const float* delp = p.delta + (b * p.H + h) * p.nq;
-
-    f32x16 acc_k[DB], acc_v[DB];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc_k[d][r] = 0.f; acc_v[d][r] = 0.f; }
-
     const int kt = k0 >> 5;
     const int nqt = (p.nq + 31) / 32;
     for (int qt = 0; qt < nqt; ++qt) {
-        const int q0 = qt * 32;
-        const int qrow = TAIL ? min(q0 + kl, p.nq - 1) : q0 + kl;
-        f32x16 s, dp;
+        if constexpr (!TAIL) {
+            const GlobalFrags<false> src{w, p.nq, kl, hi, lsep, delp, qt * 32};
+            attn_bwd_dkv_step<T, D>(src, kf, vf, p.scale_log2e, p.flags, static_cast<long>(qt) * p.flags_ld + kt, p.bias, p.bias_ld, qt * 32, k0 + kl, hi, acc_k, acc_v);
+        } else {
+            // The guarded tile is NOT attn_bwd_dkv_step: written here, in the kernel, the compiler rounds 4 of the 16 dS registers of the fp16
+            // instantiation with a fused multiply-convert (v_fma_mixlo_f16: one rounding) and the others with a multiply and a convert (two);
+            // as a step function it is optimised before it is inlined and none is fused, which moves dK by an fp16 ulp in rare elements.
+            // The body stays as it was so that the results do.  Same arithmetic as the step, with rows clamped and tails masked.
+            const int q0 = qt * 32;
+            const int qrow = min(q0 + kl, p.nq - 1);
+            f32x16 s, dp;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u16x8 qf = *reinterpret_cast<const u16x8*>(qp + static_cast<long>(qrow) * p.q_ld + 16 * ks + 8 * hi);
-            const u16x8 df = *reinterpret_cast<const u16x8*>(dop + static_cast<long>(qrow) * p.do_ld + 16 * ks + 8 * hi);
-            s = Mfma32<T>::run(__builtin_bit_cast(frag, qf), kf[ks], s);           // S  [query][key]
-            dp = Mfma32<T>::run(__builtin_bit_cast(frag, df), vf[ks], dp);         // dP [query][key]
-        }
-        // register r <-> query q0 + (r & 3) + 8 (r >> 2) + 4 hi; the lane's column is key k0 + kl
-        float sv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
-        if (p.flags && p.flags[static_cast<long>(qt) * p.flags_ld + kt]) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                if (!TAIL || (qi < p.nq && k0 + kl < p.nk)) sv[r] += p.bias[static_cast<long>(qi) * p.bias_ld + k0 + kl] * LOG2E;
+            for (int ks = 0; ks < KS; ++ks) {
+                const u16x8 qf = *reinterpret_cast<const u16x8*>(w.rp[0] + static_cast<long>(qrow) * p.q_ld + 16 * ks + 8 * hi);
+                const u16x8 df = *reinterpret_cast<const u16x8*>(w.rp[1] + static_cast<long>(qrow) * p.do_ld + 16 * ks + 8 * hi);
+                s = Mfma32<T>::run(__builtin_bit_cast(frag, qf), kf[ks], s);           // S  [query][key]
+                dp = Mfma32<T>::run(__builtin_bit_cast(frag, df), vf[ks], dp);         // dP [query][key]
             }
-        }
-        u16x8 pp[2], pd[2];
+            float sv[16];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float lv[4], dv[4];
-            if (TAIL) {
+            for (int r = 0; r < 16; ++r) sv[r] = s[r] * p.scale_log2e;
+            if (p.flags && p.flags[static_cast<long>(qt) * p.flags_ld + kt]) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (qi < p.nq && k0 + kl < p.nk) sv[r] += p.bias[static_cast<long>(qi) * p.bias_ld + k0 + kl] * LOG2E;
+                }
+            }
+            u16x8 pp[2], pd[2];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float lv[4], dv[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int qi = min(q0 + 8 * g + 4 * hi + e, p.nq - 1);
                     lv[e] = lsep[qi];
                     dv[e] = delp[qi];
                 }
-            } else {
-                const float4 l4 = *reinterpret_cast<const float4*>(lsep + q0 + 8 * g + 4 * hi);
-                const float4 d4 = *reinterpret_cast<const float4*>(delp + q0 + 8 * g + 4 * hi);
-                lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
-                dv[0] = d4.x; dv[1] = d4.y; dv[2] = d4.z; dv[3] = d4.w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * g + e;
+                    float pr = exp2f(sv[r] - lv[e]);
+                    if (q0 + 8 * g + 4 * hi + e >= p.nq) pr = 0.f;
+                    pp[r >> 3][r & 7] = from_f32<T>(pr);
+                    pd[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - dv[e]));
+                }
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * g + e;
-                float pr = exp2f(sv[r] - lv[e]);
-                if (TAIL && q0 + 8 * g + 4 * hi + e >= p.nq) pr = 0.f;
-                pp[r >> 3][r & 7] = from_f32<T>(pr);
-                pd[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - dv[e]));
-            }
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int d = 0; d < DB; ++d) {
+                    const u16x8 a_do = load_t_frag_guard(w.tp[1] + static_cast<long>(d * 32 + kl) * p.dot_ld, q0, s2, hi, p.nq);
+                    const u16x8 a_q = load_t_frag_guard(w.tp[0] + static_cast<long>(d * 32 + kl) * p.qt_ld, q0, s2, hi, p.nq);
+                    acc_v[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_do), __builtin_bit_cast(frag, pp[s2]), acc_v[d]);   // dV^T += dO^T P
+                    acc_k[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_q), __builtin_bit_cast(frag, pd[s2]), acc_k[d]);    // dK^T += Q^T dS
+                }
         }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                const unsigned short* rdo = dotp + static_cast<long>(d * 32 + kl) * p.dot_ld;
-                const unsigned short* rq = qtp + static_cast<long>(d * 32 + kl) * p.qt_ld;
-                const u16x8 a_do = TAIL ? load_t_frag_guard(rdo, q0, s2, hi, p.nq) : load_t_frag(rdo, q0, s2, hi);
-                const u16x8 a_q = TAIL ? load_t_frag_guard(rq, q0, s2, hi, p.nq) : load_t_frag(rq, q0, s2, hi);
-                acc_v[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_do), __builtin_bit_cast(frag, pp[s2]), acc_v[d]);   // dV^T += dO^T P
-                acc_k[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_q), __builtin_bit_cast(frag, pd[s2]), acc_k[d]);    // dK^T += Q^T dS
-            }
     }
     if (TAIL && k0 + kl >= p.nk) return;
-    unsigned short* okp = p.dk + b * p.dk_bs + static_cast<long>(k0 + kl) * p.dk_ld + h * D;
-    unsigned short* ovp = p.dv + b * p.dv_bs + static_cast<long>(k0 + kl) * p.dv_ld + h * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            u16x4 wk, wv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                wk[e] = from_f32<T>(acc_k[d][4 * g + e] * p.scale);
-                wv[e] = from_f32<T>(acc_v[d][4 * g + e]);
-            }
-            *reinterpret_cast<u16x4*>(okp + d * 32 + 8 * g + 4 * hi) = wk;
-            *reinterpret_cast<u16x4*>(ovp + d * 32 + 8 * g + 4 * hi) = wv;
-        }
+    attn_bwd_dkv_store16<T, D>(p, b, h, k0 + kl, hi, acc_k, acc_v);
 }
 
-// ---- LDS-staged variants (token counts that are multiples of 32) ----------------------------------------------------
-// Same math and register layout; the tile every wavefront of the block walks past (32 tokens of the OTHER side: rows and
-// their transposes) is fetched once per block with coalesced 16-byte loads, staged through LDS and shared by the four
-// waves, double buffered with the next tile's global loads in flight during the MFMAs (one barrier per tile).  The direct
-// kernels issue fragment-shaped loads (32 cache lines per instruction) from every wave.
-//   row-major tiles [32][D] with rows padded to D + 8 elements (fragment reads: 16 bytes per lane, rows 144 / 80 bytes apart)
-//   transposed tiles [D][32] with rows padded to 36 elements (two 8-byte reads per lane, rows 72 bytes apart)
-template <int D> struct BwdTile {
-    static constexpr int RS = D + 8, TS = 32 + 4;
-    static constexpr int ROWMAJ = 32 * RS, TRANS = D * TS;
-    static constexpr int CH_R = 32 * (D / 8), CH_T = D * 4;      // 16-byte chunks per row-major / transposed tile
-};
-
-__device__ __forceinline__ u16x8 lds_t_frag(const unsigned short* row, int s2, int hi) {
-    const unsigned short* pp = row + 16 * s2 + 4 * hi;
-    const u16x4 lo = *reinterpret_cast<const u16x4*>(pp);
-    const u16x4 up = *reinterpret_cast<const u16x4*>(pp + 8);
-    return u16x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-}
-
+// LDS-staged form: the query tile staged once per block (Q, dO, Q^T, dO^T).  qsplit > 1: the block walks its share of the query tiles
+// and leaves fp32 partial sums.
 template <typename T, int D>
 __global__ __launch_bounds__(256) void k_attn_bwd_dkv_lds(const AttnBwdParams p) {
     constexpr int KS = D / 16, DB = D / 32;
-    typedef BwdTile<D> TL;
+    typedef BwdStage<D, 2> Stage;
     typedef typename Mfma32<T>::frag frag;
-    constexpr int BUF = 2 * TL::ROWMAJ + 2 * TL::TRANS;          // Q rows | dO rows | Q^T | dO^T
-    __shared__ __attribute__((aligned(16))) unsigned short smem[2 * BUF];
+    __shared__ __attribute__((aligned(16))) unsigned short smem[2 * Stage::BUF];
     // log-sum-exp and delta of the 32 staged queries travel with the tiles: read straight from global memory inside the
     // step they sat on the critical path of every iteration (a step is about as long as one L2 round trip)
     __shared__ __attribute__((aligned(16))) float lsd[2][64];
@@ -309,79 +519,25 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv_lds(const AttnBwdParams p)
     const int krow = live ? k0 + kl : p.nk - 1;
     const unsigned short* kp = p.k + b * p.k_bs + static_cast<long>(krow) * p.k_ld + h * D;
     const unsigned short* vp = p.v + b * p.v_bs + static_cast<long>(krow) * p.v_ld + h * D;
-    const unsigned short* qp = p.q + b * p.q_bs + h * D;
-    const unsigned short* dop = p.dout + b * p.do_bs + h * D;
-    const unsigned short* qtp = p.qt + b * p.qt_bs + static_cast<long>(h) * D * p.qt_ld;
-    const unsigned short* dotp = p.dot + b * p.dot_bs + static_cast<long>(h) * D * p.dot_ld;
-
+    const BwdWalked w{{p.q + b * p.q_bs + h * D, p.dout + b * p.do_bs + h * D}, {p.q_ld, p.do_ld},
+                      {p.qt + b * p.qt_bs + static_cast<long>(h) * D * p.qt_ld, p.dot + b * p.dot_bs + static_cast<long>(h) * D * p.dot_ld}, {p.qt_ld, p.dot_ld}};      // Q, dO | Q^T, dO^T
     frag kf[KS], vf[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        kf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(kp + 16 * s + 8 * hi));
-        vf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(vp + 16 * s + 8 * hi));
-    }
-    const float c2 = p.scale_log2e;
+    bwd_owner_frags<T, D>(kp, vp, hi, kf, vf);
     const float* lsep = p.lse + (b * p.H + h) * p.nq;
     const float* delp = p.delta + (b * p.H + h) * p.nq;
     f32x16 acc_k[DB], acc_v[DB];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc_k[d][r] = 0.f; acc_v[d][r] = 0.f; }
+    bwd_zero(acc_k);
+    bwd_zero(acc_v);
 
-    // staging ownership: row-major chunk c -> (row c / (D/8), 8 channels at (c % (D/8)) * 8); transposed chunk c -> (row c / 4, 8 tokens at (c % 4) * 8)
-    constexpr int NR = (TL::CH_R + 255) / 256, NT = (TL::CH_T + 255) / 256;
-    u16x8 rq[NR], rdo[NR], rqt[NT], rdot[NT];
+    Stage stage;
     float4 rls = {0.f, 0.f, 0.f, 0.f};
     auto stage_load = [&](int qt_) {
-        const int q0 = qt_ * 32;
-        if (t < 16) rls = *reinterpret_cast<const float4*>((t < 8 ? lsep : delp) + q0 + 4 * (t & 7));
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_R) {
-                const int row = c / (D / 8), ch = (c % (D / 8)) * 8;
-                rq[i] = *reinterpret_cast<const u16x8*>(qp + static_cast<long>(q0 + row) * p.q_ld + ch);
-                rdo[i] = *reinterpret_cast<const u16x8*>(dop + static_cast<long>(q0 + row) * p.do_ld + ch);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_T) {
-                const int row = c >> 2, tk = (c & 3) * 8;
-                rqt[i] = *reinterpret_cast<const u16x8*>(qtp + static_cast<long>(row) * p.qt_ld + q0 + tk);
-                rdot[i] = *reinterpret_cast<const u16x8*>(dotp + static_cast<long>(row) * p.dot_ld + q0 + tk);
-            }
-        }
+        if (t < 16) rls = *reinterpret_cast<const float4*>((t < 8 ? lsep : delp) + qt_ * 32 + 4 * (t & 7));
+        stage.load(w, qt_ * 32, t);
     };
     auto stage_store = [&](int buf) {
-        unsigned short* Q = smem + buf * BUF;
-        unsigned short* DO = Q + TL::ROWMAJ;
-        unsigned short* QT = DO + TL::ROWMAJ;
-        unsigned short* DOT = QT + TL::TRANS;
         if (t < 16) *reinterpret_cast<float4*>(&lsd[buf][(t < 8 ? 0 : 32) + 4 * (t & 7)]) = rls;
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_R) {
-                const int off = (c / (D / 8)) * TL::RS + (c % (D / 8)) * 8;
-                *reinterpret_cast<u16x8*>(Q + off) = rq[i];
-                *reinterpret_cast<u16x8*>(DO + off) = rdo[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_T) {
-                const int off = (c >> 2) * TL::TS + (c & 3) * 8;          // 8-byte aligned (72-byte rows)
-                const u16x8 a = rqt[i], d = rdot[i];
-                *reinterpret_cast<u16x4*>(QT + off) = u16x4{a[0], a[1], a[2], a[3]};
-                *reinterpret_cast<u16x4*>(QT + off + 4) = u16x4{a[4], a[5], a[6], a[7]};
-                *reinterpret_cast<u16x4*>(DOT + off) = u16x4{d[0], d[1], d[2], d[3]};
-                *reinterpret_cast<u16x4*>(DOT + off + 4) = u16x4{d[4], d[5], d[6], d[7]};
-            }
-        }
+        stage.store(smem + buf * Stage::BUF, t);
     };
 
     const int kt = k0 >> 5;
@@ -395,54 +551,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv_lds(const AttnBwdParams p)
     for (int qt = qt_begin; qt < nqt; ++qt) {
         if (qt + 1 < nqt) stage_load(qt + 1);
         if (live) {
-            const int q0 = qt * 32;
-            const unsigned short* Q = smem + (qt & 1) * BUF;
-            const unsigned short* DO = Q + TL::ROWMAJ;
-            const unsigned short* QT = DO + TL::ROWMAJ;
-            const unsigned short* DOT = QT + TL::TRANS;
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const u16x8 qf = *reinterpret_cast<const u16x8*>(Q + kl * TL::RS + 16 * ks + 8 * hi);
-                const u16x8 df = *reinterpret_cast<const u16x8*>(DO + kl * TL::RS + 16 * ks + 8 * hi);
-                s = Mfma32<T>::run(__builtin_bit_cast(frag, qf), kf[ks], s);
-                dp = Mfma32<T>::run(__builtin_bit_cast(frag, df), vf[ks], dp);
-            }
-            float sv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
-            if (p.flags && p.flags[static_cast<long>(qt) * p.flags_ld + kt]) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    sv[r] += p.bias[static_cast<long>(qi) * p.bias_ld + k0 + kl] * LOG2E;
-                }
-            }
-            u16x8 pp[2], pd[2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 l4 = *reinterpret_cast<const float4*>(&lsd[qt & 1][8 * g + 4 * hi]);
-                const float4 d4 = *reinterpret_cast<const float4*>(&lsd[qt & 1][32 + 8 * g + 4 * hi]);
-                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e;
-                    const float pr = exp2f(sv[r] - lv[e]);
-                    pp[r >> 3][r & 7] = from_f32<T>(pr);
-                    pd[r >> 3][r & 7] = from_f32<T>(pr * (dp[r] - dv[e]));
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int d = 0; d < DB; ++d) {
-                    const u16x8 a_do = lds_t_frag(DOT + (d * 32 + kl) * TL::TS, s2, hi);
-                    const u16x8 a_q = lds_t_frag(QT + (d * 32 + kl) * TL::TS, s2, hi);
-                    acc_v[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_do), __builtin_bit_cast(frag, pp[s2]), acc_v[d]);
-                    acc_k[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a_q), __builtin_bit_cast(frag, pd[s2]), acc_k[d]);
-                }
+            const LdsFrags<D> src{smem + (qt & 1) * Stage::BUF, lsd[qt & 1], kl, hi};
+            attn_bwd_dkv_step<T, D>(src, kf, vf, p.scale_log2e, p.flags, static_cast<long>(qt) * p.flags_ld + kt, p.bias, p.bias_ld, qt * 32, k0 + kl, hi, acc_k, acc_v);
         }
         if (qt + 1 < nqt) stage_store((qt + 1) & 1);      // that buffer was last read in step qt - 1: every wave passed the barrier since
         __syncthreads();
@@ -461,163 +571,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv_lds(const AttnBwdParams p)
             }
         return;
     }
-    unsigned short* okp = p.dk + b * p.dk_bs + static_cast<long>(k0 + kl) * p.dk_ld + h * D;
-    unsigned short* ovp = p.dv + b * p.dv_bs + static_cast<long>(k0 + kl) * p.dv_ld + h * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            u16x4 wk, wv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                wk[e] = from_f32<T>(acc_k[d][4 * g + e] * p.scale);
-                wv[e] = from_f32<T>(acc_v[d][4 * g + e]);
-            }
-            *reinterpret_cast<u16x4*>(okp + d * 32 + 8 * g + 4 * hi) = wk;
-            *reinterpret_cast<u16x4*>(ovp + d * 32 + 8 * g + 4 * hi) = wv;
-        }
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(256) void k_attn_bwd_dq_lds(const AttnBwdParams p) {
-    constexpr int KS = D / 16, DB = D / 32;
-    typedef BwdTile<D> TL;
-    typedef typename Mfma32<T>::frag frag;
-    constexpr int BUF = 2 * TL::ROWMAJ + TL::TRANS;              // K rows | V rows | K^T
-    __shared__ __attribute__((aligned(16))) unsigned short smem[2 * BUF];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int ql = lane & 31, hi = lane >> 5;
-    const int q0 = (blockIdx.x * 4 + wave) * 32;
-    const bool live = q0 < p.nq;
-    const int h = blockIdx.y;
-    const long b = blockIdx.z;
-    const int qrow = live ? q0 + ql : p.nq - 1;
-    const unsigned short* qp = p.q + b * p.q_bs + static_cast<long>(qrow) * p.q_ld + h * D;
-    const unsigned short* dop = p.dout + b * p.do_bs + static_cast<long>(qrow) * p.do_ld + h * D;
-    const unsigned short* kp = p.k + b * p.k_bs + h * D;
-    const unsigned short* vp = p.v + b * p.v_bs + h * D;
-    const unsigned short* ktp = p.kt + b * p.kt_bs + static_cast<long>(h) * D * p.kt_ld;
-
-    frag qf[KS], dof[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        qf[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(qp + 16 * s + 8 * hi));
-        dof[s] = __builtin_bit_cast(frag, *reinterpret_cast<const u16x8*>(dop + 16 * s + 8 * hi));
-    }
-    const long stat = (b * p.H + h) * p.nq + qrow;
-    const float lse = p.lse[stat], delta = p.delta[stat];
-    const float c2 = p.scale_log2e;
-    f32x16 acc[DB];
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[d][r] = 0.f;
-
-    constexpr int NR = (TL::CH_R + 255) / 256, NT = (TL::CH_T + 255) / 256;
-    u16x8 rk[NR], rv[NR], rkt[NT];
-    auto stage_load = [&](int kt_) {
-        const int k0 = kt_ * 32;
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_R) {
-                const int row = c / (D / 8), ch = (c % (D / 8)) * 8;
-                rk[i] = *reinterpret_cast<const u16x8*>(kp + static_cast<long>(k0 + row) * p.k_ld + ch);
-                rv[i] = *reinterpret_cast<const u16x8*>(vp + static_cast<long>(k0 + row) * p.v_ld + ch);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_T) rkt[i] = *reinterpret_cast<const u16x8*>(ktp + static_cast<long>(c >> 2) * p.kt_ld + k0 + (c & 3) * 8);
-        }
-    };
-    auto stage_store = [&](int buf) {
-        unsigned short* K = smem + buf * BUF;
-        unsigned short* V = K + TL::ROWMAJ;
-        unsigned short* KT = V + TL::ROWMAJ;
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_R) {
-                const int off = (c / (D / 8)) * TL::RS + (c % (D / 8)) * 8;
-                *reinterpret_cast<u16x8*>(K + off) = rk[i];
-                *reinterpret_cast<u16x8*>(V + off) = rv[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const int c = t + 256 * i;
-            if (c < TL::CH_T) {
-                const int off = (c >> 2) * TL::TS + (c & 3) * 8;
-                const u16x8 a = rkt[i];
-                *reinterpret_cast<u16x4*>(KT + off) = u16x4{a[0], a[1], a[2], a[3]};
-                *reinterpret_cast<u16x4*>(KT + off + 4) = u16x4{a[4], a[5], a[6], a[7]};
-            }
-        }
-    };
-
-    const uint8_t* flag_row = p.flags ? p.flags + static_cast<long>(min(q0, p.nq - 32) >> 5) * p.flags_ld : nullptr;
-    const float* bias_row = p.bias ? p.bias + static_cast<long>(qrow) * p.bias_ld : nullptr;
-    const int nkt = p.nk / 32;
-    stage_load(0);
-    stage_store(0);
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-        if (kt + 1 < nkt) stage_load(kt + 1);
-        if (live) {
-            const int k0 = kt * 32;
-            const unsigned short* K = smem + (kt & 1) * BUF;
-            const unsigned short* V = K + TL::ROWMAJ;
-            const unsigned short* KT = V + TL::ROWMAJ;
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const u16x8 kf = *reinterpret_cast<const u16x8*>(K + ql * TL::RS + 16 * ks + 8 * hi);
-                const u16x8 vf = *reinterpret_cast<const u16x8*>(V + ql * TL::RS + 16 * ks + 8 * hi);
-                s = Mfma32<T>::run(__builtin_bit_cast(frag, kf), qf[ks], s);
-                dp = Mfma32<T>::run(__builtin_bit_cast(frag, vf), dof[ks], dp);
-            }
-            float sv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = s[r] * c2;
-            if (flag_row && flag_row[kt]) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 bv = *reinterpret_cast<const float4*>(bias_row + k0 + 8 * g + 4 * hi);
-                    sv[4 * g + 0] += bv.x * LOG2E;
-                    sv[4 * g + 1] += bv.y * LOG2E;
-                    sv[4 * g + 2] += bv.z * LOG2E;
-                    sv[4 * g + 3] += bv.w * LOG2E;
-                }
-            }
-            u16x8 pb[2];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pb[r >> 3][r & 7] = from_f32<T>(exp2f(sv[r] - lse) * (dp[r] - delta));
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int d = 0; d < DB; ++d) {
-                    const u16x8 a = lds_t_frag(KT + (d * 32 + ql) * TL::TS, s2, hi);
-                    acc[d] = Mfma32<T>::run(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, pb[s2]), acc[d]);
-                }
-        }
-        if (kt + 1 < nkt) stage_store((kt + 1) & 1);
-        __syncthreads();
-    }
-    if (!live) return;
-    unsigned short* op = p.dq + b * p.dq_bs + static_cast<long>(q0 + ql) * p.dq_ld + h * D;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            u16x4 w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = from_f32<T>(acc[d][4 * g + e] * p.scale);
-            *reinterpret_cast<u16x4*>(op + d * 32 + 8 * g + 4 * hi) = w;
-        }
+    attn_bwd_dkv_store16<T, D>(p, b, h, k0 + kl, hi, acc_k, acc_v);
 }
 
 // dK / dV of a query-split keys-stationary launch: the qsplit fp32 partial sums added in order, written in the 16-bit type.
@@ -1336,91 +1290,33 @@ extern "C" pf_status pf_attention_delta(const void* out, const void* dout, int d
     return PF_OK;
 }
 
-// LDS-staged kernels: whole 32-token tiles, 16-byte rows for the cooperative tile loads.  PF_ATTN_BWD_IMPL=direct: A/B switch
-static bool attn_bwd_lds(const pf_attn_bwd_desc* d) {
-    static const bool want_lds = [] { const char* e = getenv("PF_ATTN_BWD_IMPL"); return !(e && e[0] == 'd'); }();
-    const bool tail = d->nq % 32 != 0 || d->nk % 32 != 0;
-    return want_lds && !tail && d->qt_ld % 8 == 0 && d->kt_ld % 8 == 0 && d->dot_ld % 8 == 0 && d->qt_bs % 8 == 0 && d->kt_bs % 8 == 0 &&
-           d->dot_bs % 8 == 0;
-}
-
-// Query split of the keys-stationary launch: towards ~512 blocks, at least 8 query tiles (256 queries) per block.
-static int attn_bwd_qsplit(const pf_attn_bwd_desc* d) {
-    static const int on = [] { const char* e = getenv("PF_ATTN_BWD_QSPLIT"); return e ? atoi(e) : 1; }();
-    if (!on || !attn_bwd_lds(d) || (d->H * d->D) % 4 != 0) return 1;
-    const long base = cdiv(d->nk, 128) * d->H * d->B;
-    if (base >= 384) return 1;
-    const long qs = std::min<long>(cdiv(512, base), (d->nq / 32) / 8);
-    return static_cast<int>(std::max<long>(1, qs));
-}
-
-extern "C" size_t pf_attention_bwd_workspace_size(const pf_attn_bwd_desc* d) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->nq <= 0 || d->nk <= 0 || (d->D != 32 && d->D != 64)) return 0;
-    const int qs = attn_bwd_qsplit(d);
-    return qs > 1 ? static_cast<size_t>(2) * qs * d->B * d->nk * d->H * d->D * sizeof(float) : 0;
-}
-
 extern "C" pf_status pf_attention_bwd(const pf_attn_bwd_desc* d, void* stream) {
-    PF_REQUIRE(d, "pf_attention_bwd: null descriptor");
-    PF_REQUIRE(d->q && d->k && d->v && d->dout && d->qt && d->kt && d->dot && d->dq && d->dk && d->dv && d->lse && d->delta,
-               "pf_attention_bwd: null pointer");
-    PF_REQUIRE(d->D == 32 || d->D == 64, "pf_attention_bwd: head dim %d unsupported (32 or 64)", d->D);
-    PF_REQUIRE(d->B > 0 && d->H > 0 && d->nq > 0 && d->nk > 0, "pf_attention_bwd: bad sizes");
-    PF_REQUIRE(d->q_ld % 8 == 0 && d->k_ld % 8 == 0 && d->v_ld % 8 == 0 && d->do_ld % 8 == 0, "pf_attention_bwd: row-major leading dimensions must be multiples of 8");
-    PF_REQUIRE(d->qt_ld % 4 == 0 && d->kt_ld % 4 == 0 && d->dot_ld % 4 == 0 && d->qt_ld >= d->nq && d->dot_ld >= d->nq && d->kt_ld >= d->nk,
-               "pf_attention_bwd: transposed leading dimensions must be multiples of 4 and cover the token count");
-    PF_REQUIRE(d->dq_ld % 4 == 0 && d->dk_ld % 4 == 0 && d->dv_ld % 4 == 0, "pf_attention_bwd: output leading dimensions must be multiples of 4");
-    PF_REQUIRE(d->q_bs % 8 == 0 && d->k_bs % 8 == 0 && d->v_bs % 8 == 0 && d->do_bs % 8 == 0 && d->qt_bs % 4 == 0 && d->kt_bs % 4 == 0 &&
-               d->dot_bs % 4 == 0 && d->dq_bs % 4 == 0 && d->dk_bs % 4 == 0 && d->dv_bs % 4 == 0, "pf_attention_bwd: batch strides misaligned");
-    PF_REQUIRE(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->dout) && aligned16(d->qt) && aligned16(d->kt) &&
-               aligned16(d->dot) && aligned16(d->dq) && aligned16(d->dk) && aligned16(d->dv) && aligned16(d->lse) && aligned16(d->delta),
-               "pf_attention_bwd: pointers must be 16-byte aligned");
-    PF_REQUIRE((d->bias == nullptr) == (d->flags == nullptr), "pf_attention_bwd: bias and flags come together");
-    if (d->bias) {
-        PF_REQUIRE(d->nk % 4 == 0 && d->bias_ld % 4 == 0 && d->bias_ld >= d->nk && aligned16(d->bias), "pf_attention_bwd: bias needs nk %% 4 == 0 and an aligned ld >= nk");
-        PF_REQUIRE(d->flags_ld >= (d->nk + 31) / 32, "pf_attention_bwd: flags_ld too small");
-    }
+    if (const pf_status s = validate_attn_bwd_desc(d, "pf_attention_bwd")) return s;
+    // the plan of THIS launch: the query range is split only into scratch the caller handed over
+    const pf_attn_bwd_plan g = plan_attention_bwd(d, d->workspace != nullptr);
+    PF_REQUIRE(g.qsplit == 1 || (d->workspace_bytes >= g.workspace_bytes && aligned16(d->workspace)),
+               "pf_attention_bwd: workspace too small or misaligned (pf_attention_bwd_workspace_size)");
     AttnBwdParams p;
-    auto u16 = [](const void* v) { return static_cast<const unsigned short*>(v); };
-    p.q = u16(d->q); p.k = u16(d->k); p.v = u16(d->v); p.dout = u16(d->dout); p.qt = u16(d->qt); p.kt = u16(d->kt); p.dot = u16(d->dot);
-    p.dq = static_cast<unsigned short*>(d->dq); p.dk = static_cast<unsigned short*>(d->dk); p.dv = static_cast<unsigned short*>(d->dv);
-    p.H = d->H; p.nq = d->nq; p.nk = d->nk;
-    p.q_ld = d->q_ld; p.k_ld = d->k_ld; p.v_ld = d->v_ld; p.do_ld = d->do_ld; p.qt_ld = d->qt_ld; p.kt_ld = d->kt_ld; p.dot_ld = d->dot_ld;
-    p.dq_ld = d->dq_ld; p.dk_ld = d->dk_ld; p.dv_ld = d->dv_ld;
-    p.q_bs = d->q_bs; p.k_bs = d->k_bs; p.v_bs = d->v_bs; p.do_bs = d->do_bs; p.qt_bs = d->qt_bs; p.kt_bs = d->kt_bs; p.dot_bs = d->dot_bs;
-    p.dq_bs = d->dq_bs; p.dk_bs = d->dk_bs; p.dv_bs = d->dv_bs;
-    p.scale = d->scale; p.scale_log2e = d->scale * LOG2E;
-    p.bias = d->bias; p.bias_ld = d->bias_ld; p.flags = d->flags; p.flags_ld = d->flags_ld;
-    p.lse = d->lse; p.delta = d->delta;
+    attn_bwd_operands(d, p);
+    p.qsplit = g.qsplit;
+    p.part_k = g.qsplit > 1 ? static_cast<float*>(d->workspace) : nullptr;
+    p.part_v = g.qsplit > 1 ? p.part_k + g.workspace_bytes / (2 * sizeof(float)) : nullptr;
     hipStream_t st = as_stream(stream);
-    const bool tail = d->nq % 32 != 0 || d->nk % 32 != 0;        // ragged token counts: guarded loads, masked tails
-    const bool lds = attn_bwd_lds(d);
-    // keys-stationary launch with few blocks (the 128 text keys of a cross-attention: H x B blocks walking all queries; one
-    // panorama sample): the query range is split over several blocks, fp32 partial sums added in a fixed order afterwards
-    const int qsplit = d->workspace ? attn_bwd_qsplit(d) : 1;
-    p.qsplit = qsplit;
-    p.part_k = p.part_v = nullptr;
-    if (qsplit > 1) {
-        const size_t half = static_cast<size_t>(qsplit) * d->B * d->nk * d->H * d->D * sizeof(float);
-        PF_REQUIRE(d->workspace_bytes >= 2 * half && aligned16(d->workspace), "pf_attention_bwd: workspace too small or misaligned (pf_attention_bwd_workspace_size)");
-        p.part_k = static_cast<float*>(d->workspace);
-        p.part_v = p.part_k + half / sizeof(float);
-    }
-    const dim3 block(256), gq(cdiv(d->nq, 128), d->H, d->B), gk(cdiv(d->nk, 128) * qsplit, d->H, d->B);
-#define PF_BWD(DD)                                                                                                          \
-    do {                                                                                                                    \
-        if (lds) { hipLaunchKernelGGL((k_attn_bwd_dq_lds<T, DD>), gq, block, 0, st, p); hipLaunchKernelGGL((k_attn_bwd_dkv_lds<T, DD>), gk, block, 0, st, p); } \
-        else if (tail) { hipLaunchKernelGGL((k_attn_bwd_dq<T, DD, true>), gq, block, 0, st, p); hipLaunchKernelGGL((k_attn_bwd_dkv<T, DD, true>), gk, block, 0, st, p); } \
-        else { hipLaunchKernelGGL((k_attn_bwd_dq<T, DD, false>), gq, block, 0, st, p); hipLaunchKernelGGL((k_attn_bwd_dkv<T, DD, false>), gk, block, 0, st, p); } \
-    } while (0)
-    PF_DISPATCH_16(d->dtype, "pf_attention_bwd", if (d->D == 64) PF_BWD(64); else PF_BWD(32));
-#undef PF_BWD
-    if (qsplit > 1) {
-        const long total = static_cast<long>(d->B) * d->nk * (d->H * d->D / 4);
-        PF_DISPATCH_16(d->dtype, "pf_attention_bwd",
-            hipLaunchKernelGGL(k_attn_bwd_reduce<T>, dim3(cdiv(total, 256)), dim3(256), 0, st, p.part_k, p.part_v, qsplit, d->B, d->nk, d->H * d->D,
+    const dim3 block(g.threads), gq(g.dq_grid_x, g.dq_grid_y, g.dq_grid_z), gk(g.dkv_grid_x, g.dkv_grid_y, g.dkv_grid_z);
+#define PF_BWD(DQ, DKV) do { hipLaunchKernelGGL(DQ, gq, block, 0, st, p); hipLaunchKernelGGL(DKV, gk, block, 0, st, p); } while (0)
+    PF_DISPATCH_16(d->dtype, "pf_attention_bwd",
+        switch (g.kernel * 100 + d->D) {
+            case 32: PF_BWD((k_attn_bwd_dq<T, 32, false>), (k_attn_bwd_dkv<T, 32, false>)); break;
+            case 64: PF_BWD((k_attn_bwd_dq<T, 64, false>), (k_attn_bwd_dkv<T, 64, false>)); break;
+            case 132: PF_BWD((k_attn_bwd_dq<T, 32, true>), (k_attn_bwd_dkv<T, 32, true>)); break;
+            case 164: PF_BWD((k_attn_bwd_dq<T, 64, true>), (k_attn_bwd_dkv<T, 64, true>)); break;
+            case 232: PF_BWD((k_attn_bwd_dq_lds<T, 32>), (k_attn_bwd_dkv_lds<T, 32>)); break;
+            case 264: PF_BWD((k_attn_bwd_dq_lds<T, 64>), (k_attn_bwd_dkv_lds<T, 64>)); break;
+        }
+        if (g.qsplit > 1)
+            hipLaunchKernelGGL(k_attn_bwd_reduce<T>, dim3(g.reduce_grid_x), dim3(256), 0, st, p.part_k, p.part_v, g.qsplit, d->B, d->nk, d->H * d->D,
                                p.dk, p.dv, p.dk_ld, p.dv_ld, p.dk_bs, p.dv_bs));
-    }
+#undef PF_BWD
     PF_CHECK_LAUNCH("pf_attention_bwd");
     return PF_OK;
 }

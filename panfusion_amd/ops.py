@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, LwsPlan, check
+from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnBwdPlan, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, LwsPlan, check
 
 _DT = {torch.bfloat16: PF_BF16, torch.float16: PF_F16, torch.float32: PF_F32}
 
@@ -1026,11 +1026,9 @@ def attention_delta(out, dout, B, H, D, nq):
     return delta
 
 
-def attention_bwd(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, *, q_ld, k_ld, v_ld, do_ld,
-                  dq_ld, dk_ld, dv_ld, q_bs, k_bs, v_bs, do_bs, dq_bs, dk_bs, dv_bs, scale=None, bias=None, flags=None):
-    """Backward of attention(): row-major q / k / v / dout (column views allowed: leading dimension + batch stride),
-    transposed qt / kt / dot [B, H*D, tokens] (tokens contiguous; row slices of a wider transpose allowed),
-    lse / delta fp32 [B, H, nq]; writes dq, dk, dv."""
+def _attn_bwd_desc(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, q_ld, k_ld, v_ld, do_ld, dq_ld, dk_ld, dv_ld,
+                   q_bs, k_bs, v_bs, do_bs, dq_bs, dk_bs, dv_bs, scale, bias, flags):
+    """pf_attn_bwd_desc of a launch, without scratch (attention_bwd adds it where the plan asks for some)."""
     assert qt.dim() == 3 and kt.dim() == 3 and dot.dim() == 3 and qt.stride(-1) == kt.stride(-1) == dot.stride(-1) == 1
     d = AttnBwdDesc()
     d.q, d.k, d.v, d.dout = _p(q), _p(k), _p(v), _p(dout)
@@ -1044,16 +1042,36 @@ def attention_bwd(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, n
     d.qt_bs, d.kt_bs, d.dot_bs = qt.stride(0), kt.stride(0), dot.stride(0)
     d.dq_bs, d.dk_bs, d.dv_bs = dq_bs, dk_bs, dv_bs
     d.scale = scale if scale is not None else D ** -0.5
-    d.bias, d.bias_ld = _p(bias), (_ld(bias) if bias is not None else 0)
-    d.flags, d.flags_ld = _p(flags), (_ld(flags) if flags is not None else 0)
+    if bias is not None:
+        d.bias, d.bias_ld = _p(bias), _ld(bias)
+    if flags is not None:
+        d.flags, d.flags_ld = _p(flags), _ld(flags)
     d.lse, d.delta = _p(lse), _p(delta)
-    d.workspace, d.workspace_bytes = None, 0
-    nbytes = _lib.lib().pf_attention_bwd_workspace_size(C.byref(d))
-    if nbytes:
+    return d                                                # (workspace NULL: a fresh struct is zero)
+
+
+_BWD_PLAN = AttnBwdPlan()      # the launch path's plan, read at once (want_plan hands out a struct of its own)
+
+
+def attention_bwd(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, *, q_ld, k_ld, v_ld, do_ld,
+                  dq_ld, dk_ld, dv_ld, q_bs, k_bs, v_bs, do_bs, dq_bs, dk_bs, dv_bs, scale=None, bias=None, flags=None, want_plan=False):
+    """Backward of attention(): row-major q / k / v / dout (column views allowed: leading dimension + batch stride),
+    transposed qt / kt / dot [B, H*D, tokens] (tokens contiguous; row slices of a wider transpose allowed),
+    lse / delta fp32 [B, H, nq]; writes dq, dk, dv.
+    want_plan: launch nothing, allocate nothing, return the library's plan (AttnBwdPlan) of the launch."""
+    d = _attn_bwd_desc(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, q_ld, k_ld, v_ld, do_ld, dq_ld, dk_ld, dv_ld,
+                       q_bs, k_bs, v_bs, do_bs, dq_bs, dk_bs, dv_bs, scale, bias, flags)
+    g = AttnBwdPlan() if want_plan else _BWD_PLAN
+    lib, ref = _lib.lib(), C.byref(d)
+    check(lib.pf_attention_bwd_plan(ref, C.byref(g)), "pf_attention_bwd_plan")
+    if want_plan:
+        return g
+    nbytes = g.workspace_bytes
+    if nbytes:                                              # few key blocks: scratch that lets the library split the query range (pf_attn_bwd_desc.workspace)
         ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
         d.workspace, d.workspace_bytes = _p(ws), nbytes
     _traced("k_attention_bwd", 10.0 * B * H * nq * nk * D,
-            lambda: check(_lib.lib().pf_attention_bwd(C.byref(d), _stream()), "pf_attention_bwd"),
+            lambda: check(lib.pf_attention_bwd(ref, _stream()), "pf_attention_bwd"),
             "B%d H%d D%d nq%d nk%d bias%d" % (B, H, D, nq, nk, bias is not None))
 
 

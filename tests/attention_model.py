@@ -293,7 +293,10 @@ BWD_CASES = (
     [make_case("lds", B, 2, D, nq, nk, bias=bias) for D in (32, 64) for bias in (False, True) for (B, nq, nk) in ((2, 128, 320), (1, 64, 160))] +
     [make_case("ragged", 2, 2, 64, 16, 16), make_case("ragged", 2, 2, 64, 100, 128, bias=True), make_case("ragged", 2, 2, 32, 40, 72),
      make_case("whole", 1, 2, 64, 64, 96, pad4=True),
-     make_case("qsplit", 1, 2, 32, 512, 64, qs=2), make_case("qsplit", 1, 1, 64, 544, 96, qs=2), make_case("qsplit", 1, 2, 64, 768, 160, bias=True, qs=3)])
+     make_case("qsplit", 1, 2, 32, 512, 64, qs=2), make_case("qsplit", 1, 1, 64, 544, 96, qs=2), make_case("qsplit", 1, 2, 64, 768, 160, bias=True, qs=3),
+     # (appended: the seeds of the cases above follow their positions) a bias through the arms that ran without one
+     make_case("ragged", 2, 2, 32, 40, 72, bias=True), make_case("whole", 1, 2, 32, 64, 96, pad4=True, bias=True),
+     make_case("whole", 1, 2, 64, 96, 64, pad4=True, bias=True)])
 
 STAIRS = (0, 12, 3, 10, 5, 9, 2)       # climb of the row maximum per 64-key tile, log2 units: above and below the 2^8 threshold
 SPIKE_SPLIT = 20.0                     # spike key = 20 x a query row (D = 32: 163 log2 units above the rest -> the other splits' weights underflow)

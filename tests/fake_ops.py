@@ -509,7 +509,8 @@ def attention_delta(out, dout, B, H, D, nq):
 
 
 def attention_bwd(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, *, scale=None, bias=None, flags=None,
-                  **strides):
+                  want_plan=False, **strides):
+    assert not want_plan, "the CPU stand-in launches nothing: it has no plan to report"
     heads = lambda t, n: t.float().reshape(B, n, H, D).transpose(1, 2)
     qh, kh, vh, doh = heads(q, nq), heads(k, nk), heads(v, nk), heads(dout, nq)
     # the transposed operands must be the transposes of the row-major ones (the kernel reads both)

@@ -6,8 +6,6 @@ operands sit in buffers with canaries around them.  Needs an MI355X: `-m gpu`.
 
 Only the per-call switches are touched (PF_ATTENTION_PP, PF_ATTENTION_SPLIT); the arms behind once-per-process switches
 are reached through their operand layouts (a V^T / transposed leading dimension that is 4 mod 8 takes the no-LDS kernels)."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -133,22 +131,43 @@ def transposed(x, pad):
     return buf[:, :, :n]
 
 
-def run_backward(c, x, ref, dtype):
+def backward_operands(c, x, ref, dtype):
+    """Device operands of a backward case and the keywords of ops.attention_bwd: contiguous q / k / v / dout, their transposes (rows
+    padded by 4 NaN tokens under pad4), lse / delta from the reference (the bound judges the backward kernels alone), outputs in slots."""
     B, H, D, nq, nk, Cc = c.B, c.H, c.D, c.nq, c.nk, c.H * c.D
     q, k, v, dout = (t.to(DEV).contiguous() for t in (x.q, x.k, x.v, x.dout))
     pad = 4 if c.pad4 else 0
     qt, kt, dot = transposed(q, pad), transposed(k, pad), transposed(dout, pad)
-    lse, delta = ref.lse.float().to(DEV).contiguous(), ref.delta.float().to(DEV).contiguous()      # from the reference: the bound judges the backward kernels alone
+    lse, delta = ref.lse.float().to(DEV).contiguous(), ref.delta.float().to(DEV).contiguous()
     bias, flags = padded_bias(x.bias, x.flags)
-    (bq, dq), (bk, dk), (bv, dv) = slot(B, nq, Cc, dtype), slot(B, nk, Cc, dtype), slot(B, nk, Cc, dtype)
+    slots = slot(B, nq, Cc, dtype), slot(B, nk, Cc, dtype), slot(B, nk, Cc, dtype)
     w = Cc + 2 * OPAD
-    ops().attention_bwd(q, k, v, dout, qt, kt, dot, lse, delta, dq, dk, dv, B, H, D, nq, nk, q_ld=Cc, k_ld=Cc, v_ld=Cc, do_ld=Cc,
-                        dq_ld=w, dk_ld=w, dv_ld=w, q_bs=nq * Cc, k_bs=nk * Cc, v_bs=nk * Cc, do_bs=nq * Cc, dq_bs=nq * w, dk_bs=nk * w, dv_bs=nk * w,
-                        scale=x.scale, bias=bias, flags=flags)
+    args = (q, k, v, dout, qt, kt, dot, lse, delta, slots[0][1], slots[1][1], slots[2][1], B, H, D, nq, nk)
+    kw = dict(q_ld=Cc, k_ld=Cc, v_ld=Cc, do_ld=Cc, dq_ld=w, dk_ld=w, dv_ld=w, q_bs=nq * Cc, k_bs=nk * Cc, v_bs=nk * Cc, do_bs=nq * Cc,
+              dq_bs=nq * w, dk_bs=nk * w, dv_bs=nk * w, scale=x.scale, bias=bias, flags=flags)
+    return args, kw, slots
+
+
+def run_backward(c, args, kw, slots):
+    for buf, _ in slots:
+        buf.zero_()
+    ops().attention_bwd(*args, **kw)
     torch.cuda.synchronize()
-    for buf in (bq, bk, bv):                               # the slots the call does not own stay zero
+    for buf, _ in slots:                                   # the slots the call does not own stay zero
+        Cc = c.H * c.D
         assert not buf[:, :, :OPAD].any() and not buf[:, :, OPAD + Cc:].any(), "%s: wrote outside its output columns" % c.name
-    return dict(dq=dq.clone(), dk=dk.clone(), dv=dv.clone()), (qt, kt, dot)
+    return dict(dq=slots[0][1].clone(), dk=slots[1][1].clone(), dv=slots[2][1].clone())
+
+
+BWD_KERNEL = {"whole": 0, "ragged": 1, "lds": 2, "qsplit": 2}
+
+
+def assert_bwd_plan(c, args, kw):
+    """The library's plan of the launch run_backward is about to make: the kernel pair and the query split the case claims -- the bounds
+    below belong to that arm."""
+    g = ops().attention_bwd(*args, want_plan=True, **kw)
+    assert (g.kernel, g.qsplit) == (BWD_KERNEL[c.arm], c.qs), "%s plans to kernel %d, qsplit %d" % (c.name, g.kernel, g.qsplit)
+    assert (g.workspace_bytes > 0) == (c.qs > 1) == (g.reduce_grid_x > 0)
 
 
 BWD = (("dq", "dQ", "A_Q", "F_Q"), ("dk", "dK", "A_K", "F_K"), ("dv", "dV", "A_V", "F_V"))
@@ -158,15 +177,11 @@ BWD = (("dq", "dQ", "A_Q", "F_Q"), ("dk", "dK", "A_K", "F_K"), ("dv", "dV", "A_V
 @pytest.mark.parametrize("i", range(len(M.BWD_CASES)), ids=[c.name for c in M.BWD_CASES])
 def test_backward(i, dtype):
     c, x, ref = M.bwd_ref(i, dtype)
-    got, (qt, kt, dot) = run_backward(c, x, ref, dtype)
+    args, kw, slots = backward_operands(c, x, ref, dtype)
+    assert_bwd_plan(c, args, kw)
+    got = run_backward(c, args, kw, slots)
     if c.qs > 1:
-        from panfusion_amd import _lib
-        d = _lib.AttnBwdDesc()
-        d.B, d.H, d.D, d.nq, d.nk = c.B, c.H, c.D, c.nq, c.nk
-        d.qt_ld, d.kt_ld, d.dot_ld = qt.stride(-2), kt.stride(-2), dot.stride(-2)
-        d.qt_bs, d.kt_bs, d.dot_bs = qt.stride(0), kt.stride(0), dot.stride(0)
-        assert _lib.lib().pf_attention_bwd_workspace_size(C.byref(d)) > 0, "this problem should split its query range"
-        again, _ = run_backward(c, x, ref, dtype)          # partial sums are added in a fixed order
+        again = run_backward(c, args, kw, slots)           # partial sums are added in a fixed order
         assert torch.equal(again["dk"], got["dk"]) and torch.equal(again["dv"], got["dv"])
     bounds = M.backward_bounds(ref, dtype)
     fails = []
