@@ -103,6 +103,26 @@ pf_status pf_remap(const void* src, int dtype, int B, int C, int hs, int ws,
                    const float* map_x, const float* map_y, const uint8_t* mask, int map_batch,
                    int ho, int wo, int mode, void* dst, void* stream);
 
+/* external/Perspective_and_Equirectangular/mp2e.py:6-28 (called from dataset/PanoDataset.py:208-213 and
+ * models/pano/MvDiffusion.py:144,157): `m` perspective views stitched into one panorama in ONE launch,
+ *   out = sum_i p2e(img_i) p2e(tent_i) / sum_i p2e(tent_i),   `fill` where the denominator is 0,
+ * both samples with the tensor p2e semantics of pf_p2e_grid + pf_remap (grid_sample, align_corners=True, zeros
+ * outside, times the visibility mask), summed in fp32 over the cameras in index order: every term is the float
+ * pf_remap returns, and the result does not depend on the launch geometry.  tent_i is the view-sized weight image
+ * of mp2e.py:14-17, T[x] = float32(linspace(0, 1, pw/2)[x]) on the left half and float32(linspace(1, 0, pw/2)
+ * [x - pw/2]) on the right (numpy rules, in double); feather 0 = T[x] (the reference), 1 = float32(T[x] Ty[y]) with Ty
+ * the same tent over the rows.  pw must be even, and ph too with feather 1.  mp2e.py:19-21 (a blurred mask that is
+ * never used) has no counterpart.
+ *   src [B][m][C][ph][pw] (PF_F32 / PF_F16 / PF_BF16), out [B][C][H][W] fp32, weight (optional, may be NULL)
+ *   [B][1][H][W] fp32 = the denominator.  Cameras: cam_batch * m host doubles each (degrees, fov in (0, 180)),
+ *   cam_batch == B (per batch) or 1 (shared).  mode 0 = nearest, 1 = bilinear.
+ * workspace: pf_mp2e_workspace_size(B, m) bytes of device memory, 8-byte aligned (the camera constants). */
+size_t pf_mp2e_workspace_size(int B, int m);
+pf_status pf_mp2e(const void* src, int dtype, int B, int m, int C, int ph, int pw,
+                  const double* host_fov, const double* host_theta, const double* host_phi, int cam_batch,
+                  int H, int W, int mode, int feather, float fill, float* out, float* weight,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* models/pano/utils.py:92-95: (lon,lat) of every pixel of an (H,W) panorama, [H][W][2] fp32. */
 pf_status pf_equi_coords(int H, int W, float* lonlat, void* stream);
 

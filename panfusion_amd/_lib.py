@@ -134,6 +134,9 @@ SIGNATURES = {
     "pf_nearest_indices": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "pf_remap": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                          c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pf_mp2e_workspace_size": (c_size_t, [c_int, c_int]),
+    "pf_mp2e": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_dp, c_dp, c_dp, c_int, c_int, c_int, c_int, c_int,
+                        c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pf_equi_coords": (c_int, [c_int, c_int, c_void_p, c_void_p]),
     "pf_spherical_pe": (c_int, [c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p]),
     "pf_epa_tables_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

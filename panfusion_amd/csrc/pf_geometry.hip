@@ -127,13 +127,17 @@ __device__ __forceinline__ void e2p_position(const CamParams& cp, int eh, int ew
     py = la / 90.0 * cy + cy;
 }
 
-// p2e.py:9-49
-__device__ __forceinline__ void p2e_position(const CamParams& cp, int ph, int pw, int h, int w,
-                                             int y, int x, double& u, double& v, bool& visible) {
+// p2e.py:15-19: unit ray of panorama pixel (y, x), the same for every camera
+__device__ __forceinline__ void equi_pixel_ray(int h, int w, int y, int x, double& dx, double& dy, double& dz) {
     double lon = linspace_at(-180.0, 180.0, w, x) * kDeg2Rad;
     double lat = linspace_at(90.0, -90.0, h, y) * kDeg2Rad;
     double cl = cos(lat);
-    double dx = cos(lon) * cl, dy = sin(lon) * cl, dz = sin(lat);
+    dx = cos(lon) * cl, dy = sin(lon) * cl, dz = sin(lat);
+}
+
+// p2e.py:28-47: where one camera sees that ray
+__device__ __forceinline__ void ray_to_pers(const CamParams& cp, int ph, int pw, double dx, double dy, double dz,
+                                            double& u, double& v, bool& visible) {
     double ax, ay, az, bx, by, bz;
     matvec(cp.R2i, dx, dy, dz, ax, ay, az);
     matvec(cp.R1i, ax, ay, az, bx, by, bz);
@@ -143,6 +147,14 @@ __device__ __forceinline__ void p2e_position(const CamParams& cp, int ph, int pw
     u = inside ? (yy + cp.w_len) / 2.0 / cp.w_len * pw : 0.0;
     v = inside ? (-zz + cp.h_len) / 2.0 / cp.h_len * ph : 0.0;
     visible = inside && front;
+}
+
+// p2e.py:9-49
+__device__ __forceinline__ void p2e_position(const CamParams& cp, int ph, int pw, int h, int w,
+                                             int y, int x, double& u, double& v, bool& visible) {
+    double dx, dy, dz;
+    equi_pixel_ray(h, w, y, x, dx, dy, dz);
+    ray_to_pers(cp, ph, pw, dx, dy, dz, u, v, visible);
 }
 
 // kornia.remap normalisation (factor first) + torch grid_sample un-normalisation, fp32.
@@ -278,6 +290,95 @@ __global__ void k_remap(const S* src, int B, int C, int hs, int ws, const float*
             if (yin1 && xin1) acc += load_as_f32(sc + static_cast<long>(y0 + 1) * ws + x0 + 1) * w_se;
             store_from_f32(db + c * per, mask ? acc * mk : acc);
         }
+    }
+}
+
+// ---- mp2e --------------------------------------------------------------------------------------
+// mp2e.py:16-17: the feather weight of column (or row) i of n, numpy linspace in double rounded to float32
+__device__ __forceinline__ float tent_at(int n, int i) {
+    const int half = n / 2;
+    const bool rising = i < half;
+    if (half == 1) return rising ? 0.0f : 1.0f;             // numpy.linspace(a, b, 1) is [a]
+    return static_cast<float>(rising ? linspace_at(0.0, 1.0, half, i) : linspace_at(1.0, 0.0, half, i - half));
+}
+
+// mp2e.py:6-28, one thread per panorama pixel: out = sum_i p2e(img_i) p2e(tent_i) / sum_i p2e(tent_i) over the cameras in
+// index order, `fill` where the denominator is 0.  Both samples of a camera are k_remap's, tap for tap (the tent image is
+// formed on the fly: T[x], or f32(T[x] Ty[y]) with feather 1); a camera that does not see the pixel adds 0 to both sums in
+// the composition and is skipped here.  CCH channels per pass over the cameras; blockIdx.y is the batch index, so the
+// camera constants are wave-uniform loads.
+template <typename S, int CCH>
+__global__ void k_mp2e(const S* __restrict__ src, const CamParams* __restrict__ cams, int m, int C, int ph, int pw,
+                       int cam_batch, int H, int W, int mode, int feather, float fill, float* __restrict__ out,
+                       float* __restrict__ weight) {
+    const long per = static_cast<long>(H) * W;
+    const long pix = blockIdx.x * static_cast<long>(blockDim.x) + threadIdx.x;
+    if (pix >= per) return;
+    const int b = blockIdx.y;
+    const int x = pix % W, y = pix / W;
+    double dx, dy, dz;
+    equi_pixel_ray(H, W, y, x, dx, dy, dz);
+    const CamParams* cb = cams + (cam_batch == 1 ? 0 : static_cast<long>(b) * m);
+    const long cs = static_cast<long>(ph) * pw;
+    const S* sb = src + static_cast<long>(b) * m * C * cs;
+    float* ob = out + static_cast<long>(b) * C * per + pix;
+    for (int c0 = 0; c0 < C; c0 += CCH) {
+        float num[CCH], den = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CCH; ++k) num[k] = 0.0f;
+        for (int i = 0; i < m; ++i) {
+            double u, v;
+            bool vis;
+            ray_to_pers(cb[i], ph, pw, dx, dy, dz, u, v, vis);
+            if (!vis) continue;
+            const float px = sample_position(static_cast<float>(u), pw);
+            const float py = sample_position(static_cast<float>(v), ph);
+            const S* sv = sb + (static_cast<long>(i) * C + c0) * cs;
+            float term[CCH], wgt;
+            if (mode == 0) {
+                const float fx = nearbyintf(px), fy = nearbyintf(py);
+                const bool ok = fx >= 0.0f && fx < static_cast<float>(pw) && fy >= 0.0f && fy < static_cast<float>(ph);
+                if (!ok) continue;                           // both samples are 0
+                const int xi = static_cast<int>(fx), yi = static_cast<int>(fy);
+                const long off = static_cast<long>(yi) * pw + xi;
+                wgt = feather ? tent_at(pw, xi) * tent_at(ph, yi) : tent_at(pw, xi);
+#pragma unroll
+                for (int k = 0; k < CCH; ++k) term[k] = c0 + k < C ? load_as_f32(sv + k * cs + off) : 0.0f;
+            } else {
+                const float x0f = floorf(px), y0f = floorf(py);
+                const float wx = px - x0f, ex = 1.0f - wx, wy = py - y0f, sy = 1.0f - wy;
+                const float w_nw = sy * ex, w_ne = sy * wx, w_sw = wy * ex, w_se = wy * wx;
+                const int x0 = static_cast<int>(x0f), y0 = static_cast<int>(y0f);
+                const bool xin0 = x0 >= 0 && x0 < pw, xin1 = x0 + 1 >= 0 && x0 + 1 < pw;
+                const bool yin0 = y0 >= 0 && y0 < ph, yin1 = y0 + 1 >= 0 && y0 + 1 < ph;
+                const float tx0 = xin0 ? tent_at(pw, x0) : 0.0f, tx1 = xin1 ? tent_at(pw, x0 + 1) : 0.0f;
+                const float ty0 = feather && yin0 ? tent_at(ph, y0) : 1.0f, ty1 = feather && yin1 ? tent_at(ph, y0 + 1) : 1.0f;
+                wgt = 0.0f;
+                if (yin0 && xin0) wgt = (tx0 * ty0) * w_nw;
+                if (yin0 && xin1) wgt += (tx1 * ty0) * w_ne;
+                if (yin1 && xin0) wgt += (tx0 * ty1) * w_sw;
+                if (yin1 && xin1) wgt += (tx1 * ty1) * w_se;
+#pragma unroll
+                for (int k = 0; k < CCH; ++k) {
+                    float acc = 0.0f;
+                    if (c0 + k < C) {
+                        const S* sc = sv + k * cs;
+                        if (yin0 && xin0) acc = load_as_f32(sc + static_cast<long>(y0) * pw + x0) * w_nw;
+                        if (yin0 && xin1) acc += load_as_f32(sc + static_cast<long>(y0) * pw + x0 + 1) * w_ne;
+                        if (yin1 && xin0) acc += load_as_f32(sc + static_cast<long>(y0 + 1) * pw + x0) * w_sw;
+                        if (yin1 && xin1) acc += load_as_f32(sc + static_cast<long>(y0 + 1) * pw + x0 + 1) * w_se;
+                    }
+                    term[k] = acc;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CCH; ++k) num[k] += term[k] * wgt;      // two roundings (-ffp-contract=off)
+            den += wgt;
+        }
+#pragma unroll
+        for (int k = 0; k < CCH; ++k)
+            if (c0 + k < C) ob[(c0 + k) * per] = den == 0.0f ? fill : num[k] / den;
+        if (c0 == 0 && weight) weight[static_cast<long>(b) * per + pix] = den;
     }
 }
 
@@ -506,6 +607,59 @@ extern "C" pf_status pf_remap(const void* src, int dtype, int B, int C, int hs, 
     else
         PF_REQUIRE(false, "pf_remap: unsupported dtype %d", dtype);
     PF_CHECK_LAUNCH("pf_remap");
+    return PF_OK;
+}
+
+static size_t round256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+extern "C" size_t pf_mp2e_workspace_size(int B, int m) {
+    return B > 0 && m > 0 ? round256(sizeof(CamParams) * static_cast<size_t>(B) * m) : 0;
+}
+
+template <typename S>
+static void launch_mp2e(const void* src, const CamParams* cams, int B, int m, int C, int ph, int pw, int cam_batch, int H,
+                        int W, int mode, int feather, float fill, float* out, float* weight, hipStream_t st) {
+    const dim3 grid(cdiv(static_cast<long>(H) * W, 256), B), block(256);
+    hipLaunchKernelGGL((k_mp2e<S, 4>), grid, block, 0, st, static_cast<const S*>(src), cams, m, C, ph, pw, cam_batch, H, W,
+                       mode, feather, fill, out, weight);
+}
+
+extern "C" pf_status pf_mp2e(const void* src, int dtype, int B, int m, int C, int ph, int pw, const double* fov,
+                             const double* theta, const double* phi, int cam_batch, int H, int W, int mode, int feather,
+                             float fill, float* out, float* weight, void* workspace, size_t ws_bytes, void* stream) {
+    PF_REQUIRE(src && out && workspace, "pf_mp2e: null pointer");
+    PF_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % sizeof(double) == 0, "pf_mp2e: workspace must be 8-byte aligned");
+    PF_REQUIRE(fov && theta && phi, "pf_mp2e: cameras missing");
+    PF_REQUIRE(B > 0 && B <= 65535 && m > 0 && C > 0, "pf_mp2e: bad sizes (B %d, m %d, C %d)", B, m, C);
+    PF_REQUIRE(ph > 1 && pw > 1 && H > 1 && W > 1, "pf_mp2e: sizes must be > 1");
+    PF_REQUIRE(pw % 2 == 0, "pf_mp2e: view width %d must be even (the tent has two halves)", pw);
+    PF_REQUIRE(feather == 0 || feather == 1, "pf_mp2e: feather must be 0 (horizontal) or 1 (both)");
+    PF_REQUIRE(feather == 0 || ph % 2 == 0, "pf_mp2e: view height %d must be even with feather both", ph);
+    PF_REQUIRE(mode == 0 || mode == 1, "pf_mp2e: mode must be 0 (nearest) or 1 (bilinear)");
+    PF_REQUIRE(dtype == PF_F32 || dtype == PF_F16 || dtype == PF_BF16, "pf_mp2e: unsupported dtype %d", dtype);
+    PF_REQUIRE(cam_batch == 1 || cam_batch == B, "pf_mp2e: cam_batch must be 1 or B");
+    PF_REQUIRE(ws_bytes >= pf_mp2e_workspace_size(B, m), "pf_mp2e: workspace too small (%zu < %zu)", ws_bytes,
+               pf_mp2e_workspace_size(B, m));
+    PF_REQUIRE(isfinite(fill), "pf_mp2e: fill must be finite");
+    const int ncam = cam_batch * m;
+    for (int i = 0; i < ncam; ++i)
+        PF_REQUIRE(fov[i] > 0.0 && fov[i] < 180.0, "pf_mp2e: fov[%d] = %g outside (0, 180)", i, fov[i]);
+    hipStream_t st = as_stream(stream);
+    CamParams* cams = static_cast<CamParams*>(workspace);
+    for (int c0 = 0; c0 < ncam; c0 += CAM_BATCH) {         // camera constants into the caller's workspace, by value
+        const int n = ncam - c0 < CAM_BATCH ? ncam - c0 : CAM_BATCH;
+        CamBatch batch;
+        fill_batch(fov, theta, phi, c0, n, ph, pw, &batch);
+        constexpr int WORDS = sizeof(CamParams) / sizeof(double);
+        hipLaunchKernelGGL(k_store_cams, dim3(cdiv(n * WORDS, 256)), dim3(256), 0, st, batch, n, cams + c0);
+    }
+    if (dtype == PF_F32)
+        launch_mp2e<float>(src, cams, B, m, C, ph, pw, cam_batch, H, W, mode, feather, fill, out, weight, st);
+    else if (dtype == PF_BF16)
+        launch_mp2e<RawBf16>(src, cams, B, m, C, ph, pw, cam_batch, H, W, mode, feather, fill, out, weight, st);
+    else
+        launch_mp2e<RawF16>(src, cams, B, m, C, ph, pw, cam_batch, H, W, mode, feather, fill, out, weight, st);
+    PF_CHECK_LAUNCH("pf_mp2e");
     return PF_OK;
 }
 
@@ -881,8 +1035,6 @@ extern "C" pf_status pf_py360_c2e(const void* cube, int dtype, int n, int face_w
     PF_CHECK_LAUNCH("pf_py360_c2e");
     return PF_OK;
 }
-
-static size_t round256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 extern "C" size_t pf_epa_tables_workspace_size(int ncam, int ph, int pw, int eh, int ew) {
     size_t dense = round256(static_cast<size_t>(ncam) * ph * pw * eh * ew * sizeof(float));

@@ -122,6 +122,32 @@ def remap(src, map_x, map_y, mode, mask=None):
     return out
 
 
+FEATHERS = {"horizontal": 0, "both": 1}
+
+
+def mp2e(src, fov, theta, phi, out_hw, mode="bilinear", feather="horizontal", fill=255.0, want_weight=False):
+    """src (B, m, C, ph, pw) (fp32 / 16-bit) -> the stitched panorama (B, C, H, W) fp32 (pf_mp2e), and the summed feather weight
+    (B, 1, H, W) with ``want_weight``.  Cameras in degrees: B*m values each (per batch), or m shared by the whole batch."""
+    if src.dim() != 5:
+        raise ValueError("mp2e: src must be (B, m, C, ph, pw), got %s" % (tuple(src.shape),))
+    if mode not in ("nearest", "bilinear") or feather not in FEATHERS:
+        raise ValueError("mp2e: mode must be nearest or bilinear and feather one of %s, got %r, %r" % (sorted(FEATHERS), mode, feather))
+    src = src.contiguous()
+    B, m, Cc, ph, pw = src.shape
+    n, keep, (f, t, p) = _cams(fov, theta, phi)
+    if n != m and n != B * m:
+        raise ValueError("mp2e: %d cameras for %d views (batch %d)" % (n, m, B))
+    H, W = out_hw
+    out = torch.empty(B, Cc, H, W, device=src.device, dtype=torch.float32)
+    weight = torch.empty(B, 1, H, W, device=src.device, dtype=torch.float32) if want_weight else None
+    nbytes = _lib.lib().pf_mp2e_workspace_size(B, m)
+    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
+    check(_lib.lib().pf_mp2e(_p(src), dt(src), B, m, Cc, ph, pw, f, t, p, B if n == B * m else 1, H, W,
+                             {"nearest": 0, "bilinear": 1}[mode], FEATHERS[feather], float(fill), _p(out), _p(weight), _p(ws),
+                             nbytes, _stream()), "pf_mp2e")
+    return (out, weight) if want_weight else out
+
+
 def equi_coords(H, W, device):
     out = torch.empty(H, W, 2, device=device, dtype=torch.float32)
     check(_lib.lib().pf_equi_coords(H, W, _p(out), _stream()), "pf_equi_coords")

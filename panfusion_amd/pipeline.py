@@ -134,6 +134,24 @@ def init_noise(pano_noise, cameras, pers_h, pers_w):
     return pano_noise, noise.unflatten(0, (bs, m))
 
 
+def stitch_views(images, cameras, out_hw, **kw):
+    """The perspective branch seen as a panorama: the m views of a run stitched by ``mp2e`` (feathered where they overlap).
+    images: the uint8 views (b, m, h, w, 3) that ``vae.decode_views_and_pano`` returns, or a float tensor (b, m, C, h, w), on
+    the GPU; cameras: dict of (b, m) (FoV, theta, phi in degrees, as the loops take them); out_hw: the panorama size in
+    pixels.  Returns float32 (b, C, H, W) on the scale of the input; ``kw`` (mode, feather, fill, return_weight) goes to mp2e."""
+    from .external.Perspective_and_Equirectangular.mp2e import mp2e
+    if not isinstance(images, torch.Tensor) or images.dim() != 5:
+        raise ValueError("stitch_views: images (b, m, h, w, 3) uint8 or (b, m, C, h, w) float expected, got %s"
+                         % (getattr(images, "shape", type(images)),))
+    if images.dtype == torch.uint8:
+        images = images.permute(0, 1, 4, 2, 3).float()
+    want = tuple(images.shape[:2])
+    for k in ("FoV", "theta", "phi"):
+        if tuple(cameras[k].shape) != want:
+            raise ValueError("stitch_views: cameras[%r] must be %s, got %s" % (k, want, tuple(cameras[k].shape)))
+    return mp2e(images, cameras["FoV"].reshape(-1), cameras["theta"].reshape(-1), cameras["phi"].reshape(-1), out_hw, **kw)
+
+
 def _keep_mask(gen):
     """An image-resolution mask (n, 1, 8h, 8w), 1 = generate -> the latent mask (n, 1, h, w): a latent pixel is kept (0) only
     if all 64 pixels of its 8x8 block are known (mask < 0.5, diffusers' binarisation)."""
@@ -257,6 +275,24 @@ class KnownRegion:
         equi, covered = p2e(image.float(), [fov], [theta], [phi], (8 * pano_hw[0], 8 * pano_hw[1]))
         pano = torch.where(covered, equi, torch.zeros((), device=equi.device))
         return cls.from_panorama(vae_encoder, pano[None], (~covered).float()[None], cameras, view_hw)
+
+    @classmethod
+    def from_views(cls, vae_encoder, images, fovs, thetas, phis, cameras, pano_hw, view_hw, feather="both"):
+        """Outpaint from several photos: images (n, 3, hi, wi) in [-1, 1] on the GPU, photo i seen with horizontal field of view
+        fovs[i] at (thetas[i], phis[i]) degrees, are stitched (mp2e, bilinear, fill 0) into a panorama of 8 pano_hw pixels,
+        feathered where they overlap; the pixels that no photo covers with positive weight are generated; then from_panorama.
+        pano_hw / view_hw: the panorama / view LATENT sizes.  The feather tent is 0 on a photo's outermost columns (and rows,
+        with feather="both"), so one photo through from_views covers slightly less than the same photo through from_view."""
+        from .external.Perspective_and_Equirectangular.mp2e import mp2e
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError("KnownRegion.from_views: images (n, 3, h, w) expected, got %s" % (getattr(images, "shape", type(images)),))
+        n = images.shape[0]
+        if not len(fovs) == len(thetas) == len(phis) == n:
+            raise ValueError("KnownRegion.from_views: %d images need %d cameras, got %d / %d / %d"
+                             % (n, n, len(fovs), len(thetas), len(phis)))
+        pano, weight = mp2e(images.float(), fovs, thetas, phis, (8 * pano_hw[0], 8 * pano_hw[1]), "bilinear", feather=feather,
+                            fill=0.0, return_weight=True)
+        return cls.from_panorama(vae_encoder, pano[None, None], (weight == 0).float()[None, None], cameras, view_hw)
 
     def check(self, latents, pano_latent):
         """ValueError unless the known content fits the loop's latents (batch 1) and the masks lie in [0, 1]."""
