@@ -840,6 +840,48 @@ pf_status pf_amax_f32(const float* x, long n, float* state, int reset, void* str
 pf_status pf_pow2_scale(float* state, void* stream);
 pf_status pf_scale_f32(const float* x, long n, const float* state, int index, int out_dtype, void* y, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The FAED metric's encoder (models/faed/modules.py Encoder, models/faed/FAED.py get_activation): wide-kernel,
+ * narrow-channel convolutions that are periodic in longitude.
+ * ------------------------------------------------------------------------------------------ */
+
+/* One convolution of the FAED encoder, CircularPadding + nn.Conv2d(padding = 0) of models/faed/modules.py:5-36 with the bias and the
+ * evaluation-mode BatchNorm folded into a per-channel affine map, as an implicit GEMM on MFMA (fp16 operands, fp32 sums):
+ *
+ *   out[img][y][x][n] = act(fma(sum_{ky,kx,c} x[img][y*stride - pad + ky][(x*stride - pad + kx) mod w][c] * weight[n][ky][kx][c],
+ *                               scale[n], shift[n])) (+ residual[img][y][x][n])
+ *
+ * Geometry: (ksize, stride) is (3 | 5 | 7 | 9, 1) with pad = (ksize - 1) / 2, or (4, 2) with pad = 1 and even h and w.  Columns are
+ * periodic (w >= pad), rows outside [0, h) read zero.  h_out = (h + 2 pad - ksize) / stride + 1, w_out likewise.
+ * x: PF_F16 NHWC [n_img][h][w][c_in], c_in in {32, 64, 128}.  The image layer (downconv1_rgb) instead takes the evaluation loop's tensor
+ *    as delivered: x_dtype PF_U8 or PF_F32, planar [n_img][3][h][w] on the 0..255 scale, c_in = 3, ksize = 9, n_out = 32; v / 127.5 - 1
+ *    (FAED.py:70) is applied in fp32 and rounded to fp16 while the tile is staged.
+ * weight: fp16 [n_out][ksize][ksize][c_in], n_out in {32, 64, 128}.  scale, shift: fp32 [n_out].  relu: 0 / 1, applied before the
+ * residual (fp16 [M][n_out], may be NULL; ResBlock has no activation after its sum).  out: PF_F16 or PF_F32 [M][n_out],
+ * M = n_img * h_out * w_out.  No tensor may hold 2^31 elements or more.  A sum's order is the same at every position. */
+typedef struct {
+    const void* x;
+    int x_dtype;
+    int n_img, h, w, c_in;
+    const void* weight;
+    int n_out, ksize, stride;
+    const float* scale;
+    const float* shift;
+    int relu;
+    const void* residual;
+    void* out;
+    int out_dtype;
+} pf_pano_conv_desc;
+pf_status pf_pano_conv(const pf_pano_conv_desc* desc, void* stream);
+/* The output rows of the tile one workgroup of pf_pano_conv owns for this geometry (no launch): 16 at stride 1 with ksize 5, 7 or 9
+ * from 512 tiles of 16 x 16 on (two workgroups for each of the chip's 256 CUs), else 8; the environment's PF_PANO_CONV_ROWS = 2 | 4
+ * forces 8 | 16 where both forms exist.  The two forms give identical bits.  0: a geometry pf_pano_conv rejects. */
+int pf_pano_conv_tile_rows(int ksize, int stride, int n_img, int h, int w);
+
+/* FAED.py:72-77: x fp32 [n][h][w][C] (the encoder's output) -> out fp32 [n][C * h], out[i][c * h + y] = weight[y] * mean_x x[i][y][x][c];
+ * the mean is a sum in column order divided by w.  weight: fp32 [h] on the device (the caller's cos(linspace(pi/2, -pi/2, h))). */
+pf_status pf_faed_features(const float* x, int n, int h, int w, int C, const float* weight, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,16 @@ class AttnBwdPlan(C.Structure):
     ]
 
 
+class PanoConvDesc(C.Structure):
+    """pf_pano_conv_desc"""
+    _fields_ = [
+        ("x", c_void_p), ("x_dtype", c_int), ("n_img", c_int), ("h", c_int), ("w", c_int), ("c_in", c_int),
+        ("weight", c_void_p), ("n_out", c_int), ("ksize", c_int), ("stride", c_int),
+        ("scale", c_void_p), ("shift", c_void_p), ("relu", c_int), ("residual", c_void_p),
+        ("out", c_void_p), ("out_dtype", c_int),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/panfusion_hip.h declares
 SIGNATURES = {
     "pf_version": (c_int, []),
@@ -241,6 +251,9 @@ SIGNATURES = {
     "pf_amax_f32": (c_int, [c_void_p, c_long, c_void_p, c_int, c_void_p]),
     "pf_pow2_scale": (c_int, [c_void_p, c_void_p]),
     "pf_scale_f32": (c_int, [c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "pf_pano_conv": (c_int, [C.POINTER(PanoConvDesc), c_void_p]),
+    "pf_pano_conv_tile_rows": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "pf_faed_features": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

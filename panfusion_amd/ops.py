@@ -1267,3 +1267,62 @@ def crop_width_bwd(dy, crop):
     out = torch.empty(n, h, wc + 2 * crop, Cc, device=dy.device, dtype=torch.float32)
     check(_lib.lib().pf_crop_width_bwd(_p(dy), n, h, wc + 2 * crop, Cc, crop, _p(out), _stream()), "pf_crop_width_bwd")
     return out
+
+
+# ---------------------------------------------------------------------------- FAED encoder
+_PANO_X = {torch.float16: PF_F16, torch.uint8: _lib.PF_U8, torch.float32: PF_F32}
+
+
+def pano_conv(x, weight, scale, shift, ksize, stride, relu=False, residual=None, out_dtype=torch.float16, out=None):
+    """One convolution of the FAED encoder (pf_pano_conv): periodic columns, zero rows, scale / shift epilogue, optional ReLU and residual.
+    x is fp16 NHWC [n, h, w, c_in], or the image as delivered: uint8 / fp32 NCHW [n, 3, h, w] on the 0..255 scale (normalised while
+    staged).  weight fp16 [n_out, k, k, c_in]; scale, shift fp32 [n_out]; residual fp16 [n, h_out, w_out, n_out].  -> [n, h_out, w_out, n_out]."""
+    if x.dtype not in _PANO_X:
+        raise ValueError("pano_conv: x must be float16 (NHWC) or uint8 / float32 (the NCHW image), got %s" % x.dtype)
+    image = x.dtype != torch.float16
+    x = x.contiguous()
+    if image:
+        n, c_in, h, w = x.shape
+    else:
+        n, h, w, c_in = x.shape
+    n_out = weight.shape[0]
+    if tuple(weight.shape) != (n_out, ksize, ksize, c_in) or weight.dtype != torch.float16 or not weight.is_contiguous():
+        raise ValueError("pano_conv: weight must be contiguous float16 [n_out, %d, %d, %d], got %s %s" % (ksize, ksize, c_in, weight.dtype, tuple(weight.shape)))
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v.dtype != torch.float32 or v.numel() != n_out or not v.is_contiguous():
+            raise ValueError("pano_conv: %s must be contiguous float32 [%d]" % (name, n_out))
+    pad = 1 if stride == 2 else (ksize - 1) // 2
+    h_out, w_out = (h + 2 * pad - ksize) // max(stride, 1) + 1, (w + 2 * pad - ksize) // max(stride, 1) + 1
+    if residual is not None and (residual.dtype != torch.float16 or residual.numel() != n * h_out * w_out * n_out or not residual.is_contiguous()):
+        raise ValueError("pano_conv: residual must be contiguous float16 [%d, %d, %d, %d]" % (n, h_out, w_out, n_out))
+    if out is None:
+        out = torch.empty(n, max(h_out, 0), max(w_out, 0), n_out, device=x.device, dtype=out_dtype)
+    elif out.dtype != out_dtype or out.numel() != n * h_out * w_out * n_out or not out.is_contiguous():
+        raise ValueError("pano_conv: out must be contiguous %s [%d, %d, %d, %d]" % (out_dtype, n, h_out, w_out, n_out))
+    d = _lib.PanoConvDesc()
+    d.x, d.x_dtype, d.n_img, d.h, d.w, d.c_in = _p(x), _PANO_X[x.dtype], n, h, w, c_in
+    d.weight, d.n_out, d.ksize, d.stride = _p(weight), n_out, ksize, stride
+    d.scale, d.shift, d.relu, d.residual = _p(scale), _p(shift), int(bool(relu)), _p(residual)
+    d.out, d.out_dtype = _p(out), _DT.get(out_dtype, -1)
+    flops = 2.0 * n * h_out * w_out * n_out * ksize * ksize * c_in
+    _traced("pano_conv", flops, lambda: check(_lib.lib().pf_pano_conv(C.byref(d), _stream()), "pf_pano_conv"))
+    return out
+
+
+def pano_conv_tile_rows(ksize, stride, n, h, w):
+    """The output rows (8 or 16) of the tile a workgroup of pano_conv owns for n images of h x w (pf_pano_conv_tile_rows; no launch)."""
+    rows = _lib.lib().pf_pano_conv_tile_rows(ksize, stride, n, h, w)
+    if rows == 0:
+        raise ValueError("pano_conv_tile_rows: pano_conv does not take ksize %d, stride %d on %d x %d x %d" % (ksize, stride, n, h, w))
+    return rows
+
+
+def faed_features(x, weight):
+    """The encoder's output x fp32 [n, h', w', C] -> [n, C h'] fp32: mean over w', times weight[y], channel-major (pf_faed_features)."""
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or weight.numel() != x.shape[1]:
+        raise ValueError("faed_features: x must be float32 [n, h, w, C] and weight float32 [h]")
+    x, weight = x.contiguous(), weight.contiguous()
+    n, h, w, Cc = x.shape
+    out = torch.empty(n, Cc * h, device=x.device, dtype=torch.float32)
+    check(_lib.lib().pf_faed_features(_p(x), n, h, w, Cc, _p(weight), _p(out), _stream()), "pf_faed_features")
+    return out

@@ -152,6 +152,17 @@ def stitch_views(images, cameras, out_hw, **kw):
     return mp2e(images, cameras["FoV"].reshape(-1), cameras["theta"].reshape(-1), cameras["phi"].reshape(-1), out_hw, **kw)
 
 
+def faed(real_panos, generated_panos, metric):
+    """The Fréchet Auto-Encoder Distance between two sets of panoramas ([N, 3, H, W], uint8 or float on the 0..255 scale, at least two
+    each; a list of such batches is taken batch by batch) through ``metric``, a ``models.faed.FrechetAutoEncoderDistance``.  The
+    metric is reset first and keeps the accumulated states afterwards (``merge`` them across ranks before ``compute``)."""
+    metric.reset()
+    for panos, real in ((real_panos, True), (generated_panos, False)):
+        for batch in ([panos] if isinstance(panos, torch.Tensor) else panos):
+            metric.update(batch, real)
+    return metric.compute()
+
+
 def _keep_mask(gen):
     """An image-resolution mask (n, 1, 8h, 8w), 1 = generate -> the latent mask (n, 1, h, w): a latent pixel is kept (0) only
     if all 64 pixels of its 8x8 block are known (mask < 0.5, diffusers' binarisation)."""
