@@ -177,6 +177,32 @@ pf_status pf_groupnorm_from_partials(const float* part0, int c0, int rows0, cons
                                      int n_img, int hw, int groups, float eps, const float* gamma, const float* beta,
                                      float* scale, float* shift, void* stream);
 
+/* The whole plan of one GroupNorm statistics problem: which of the three producers runs, with what chunking, grids and workspace. */
+enum { PF_GN_DIRECT = 1, PF_GN_TWO_STAGE = 2, PF_GN_FROM_PARTIALS = 3 };
+typedef struct {
+    int arm;               /* PF_GN_DIRECT: one launch, a block per (image, group), for hw * C / groups <= PF_GN_DIRECT_MAX (32768; 0 = never;
+                            * read once per process) and n_img * hw * C <= 4 Mi;  PF_GN_TWO_STAGE: chunk partials, then k_gn_finalize;
+                            * PF_GN_FROM_PARTIALS: pf_groupnorm_from_partials;  0: refused -- every other member is 0                        */
+    int partials_refused;  /* 1: moments were offered (rows0 > 0, and rows1 > 0 with a second source) but cannot serve -- odd channels per
+                            * group or source, an image that is not whole runs of rows0 and rows1 rows, too many pairs per group -- so the
+                            * plan is that of the statistics pass                                                                           */
+    int ppc;               /* two-stage: pixels per chunk, 8 .. 64 (more where hw > 64 * 256, fewer where hw < 8)                             */
+    int nchunks;           /* two-stage: chunks per image, ceil(hw / ppc)                                                                    */
+    int pix_par;           /* two-stage: pixels a block reads in parallel, 256 / min(C / 8, 256)                                             */
+    unsigned lds_bytes;    /* two-stage: dynamic LDS of k_gn_partial, 2 fp32 arrays [pix_par][C]; refused above 64 KiB                       */
+    int gpb;               /* from partials: groups per block, 8 / 4 / 2 / 1 by parts per image, halved until a block holds <= 512 pairs     */
+    int pairs_per_block;   /* from partials: column pairs of a full block, gpb * C / groups / 2 (a ragged last block holds fewer)            */
+    int slices;            /* from partials: slices of the parts that walk them side by side in a full block, 256 / pairs_per_block
+                            * (1 above 128 pairs) -- the number k_gn_finalize_cols derives for itself                                        */
+    unsigned grid_x, grid_y;   /* the first launch: (n_img, groups) direct, (nchunks, n_img) two-stage, (n_img, ceil(groups / gpb)) partials */
+    unsigned grid2_x, grid2_y; /* two-stage: k_gn_finalize, (n_img, ceil(groups / 8)); otherwise 0                                          */
+    size_t workspace_bytes;    /* what pf_groupnorm_stats / _wrap require (of the direct arm too: n_img * nchunks * 128 floats); partials: 0  */
+} pf_gn_plan;
+/* Reads no pointer and needs no GPU.  rows0 / rows1: rows per part of the moments attached to the sources (0: none; rows1 is not looked
+ * at when c1 = 0).  A circular wrap (pf_groupnorm_stats_wrap) changes only the counted pixels: its plan is that of hw = h * w without
+ * moments.  PF_ERR_ARG, the launch's own message and an all-zero plan for a problem the launch refuses. */
+pf_status pf_groupnorm_plan(int n_img, int hw, int c0, int c1, int groups, int dtype, int rows0, int rows1, pf_gn_plan* out);
+
 /* y = act(x*scale + shift), act 0 = identity, 1 = SiLU (scale = shift = NULL: y = act(x)).  Same concat
  * convention.  dtype = type of the sources (16-bit or PF_F32).  Output:
  *   out_dtype 16-bit, out_split 0:  y [n_img][hw][C]
@@ -200,6 +226,14 @@ pf_status pf_scale_shift_act_pair(const void* x0, int c0, const void* x1, int c1
  * dtype: type of x (16-bit == out_dtype, or PF_F32); out_dtype: 16-bit type of y. */
 pf_status pf_layernorm(const void* x, const float* pe, long pe_rows, int dtype, long rows, int C,
                        const float* gamma, const float* beta, float eps, int out_dtype, void* y, void* stream);
+/* The plan of pf_layernorm and pf_layernorm_bwd (below) on [rows][C]. */
+typedef struct {
+    int rows_per_wave;   /* forward: 4 rows per wavefront in flight for C <= 512 and rows >= 4096, else 1                                  */
+    unsigned grid_x;     /* forward: blocks of 4 wavefronts, ceil(rows / (4 rows_per_wave))                                               */
+    int bwd_parts;       /* backward: blocks, each leaving one row of the [2][bwd_parts][C] partials: ceil(rows / 4), at most 512         */
+} pf_ln_plan;
+/* Reads no pointer.  PF_ERR_ARG, the launch's message and an all-zero plan for rows <= 0 or a C that either direction refuses. */
+pf_status pf_layernorm_plan(long rows, int C, pf_ln_plan* out);
 
 /* Sampling of the VAE posterior (diffusers DiagonalGaussianDistribution.sample, PanoGenerator.py:214-225):
  * moments fp32 NHWC [n][hw][2L] = (mean | logvar), eps fp32 NCHW [n][L][hw] ->
@@ -773,6 +807,23 @@ pf_status pf_groupnorm_param_grads(const void* x0, int c0, const void* x1, int c
                                    const float* scale, const float* shift, const float* unit_scale, const float* unit_shift,
                                    int act, const float* dy, float* dgamma_dbeta, void* workspace, size_t workspace_bytes,
                                    void* stream);
+/* The plan of pf_groupnorm_bwd and of the pf_groupnorm_param_grads of the same tensor: both walk an image in the same chunks. */
+typedef struct {
+    int ppc;                      /* pixels per chunk: 64, halved down to 8 while an image has fewer than 16 chunks                        */
+    int chunks;                   /* chunks per image, ceil(hw / ppc)                                                                     */
+    int pix_par;                  /* pixels a block reads in parallel, 256 / min(C / 8, 256)                                              */
+    unsigned bwd_lds_bytes;       /* dynamic LDS of k_gn_bwd_partial, 4 fp32 arrays [pix_par][C]; refused above 64 KiB                     */
+    unsigned param_lds_bytes;     /* dynamic LDS of k_gn_param_partial, 2 such arrays; refused above 64 KiB                                */
+    unsigned partial_grid_x, partial_grid_y;   /* both partial kernels: (chunks, n_img)                                                  */
+    unsigned finalize_grid_x;     /* k_gn_bwd_finalize: n_img                                                                            */
+    unsigned apply_grid_x, apply_grid_y;       /* k_gn_bwd_apply: (ceil(hw * C / 8 / 256), n_img)                                         */
+    size_t bwd_workspace_bytes;   /* pf_groupnorm_bwd: n_img * (chunks + 1) * groups * 4 floats                                           */
+    size_t param_partial_bytes;   /* pf_groupnorm_param_grads: the [n_img * chunks][2 C] fp32 partials at the head of its workspace ...    */
+    size_t param_workspace_bytes; /* ... and with the pf_colsum workspace that reduces them behind                                       */
+} pf_gn_bwd_plan;
+/* Reads no pointer.  groups > 0: both launches; groups = 0: pf_groupnorm_param_grads alone, which knows no groups and has half the LDS
+ * to fit (the members of pf_groupnorm_bwd are 0 then).  PF_ERR_ARG, the launch's message and an all-zero plan for a refused problem. */
+pf_status pf_groupnorm_bwd_plan(int n_img, int hw, int c0, int c1, int groups, pf_gn_bwd_plan* out);
 
 /* dz = dy * silu'(z), z 16-bit or PF_F32 [n] (a pre-activation the forward kept), dy / dz fp32: the SiLUs of the ControlNet's
  * conditioning embedding and of the timestep embedding under autograd (diffusers ControlNetConditioningEmbedding /

@@ -88,6 +88,33 @@ class LwsPlan(C.Structure):
     ]
 
 
+PF_GN_DIRECT, PF_GN_TWO_STAGE, PF_GN_FROM_PARTIALS = 1, 2, 3
+
+
+class GnPlan(C.Structure):
+    """pf_gn_plan"""
+    _fields_ = [
+        ("arm", c_int), ("partials_refused", c_int), ("ppc", c_int), ("nchunks", c_int), ("pix_par", c_int), ("lds_bytes", C.c_uint),
+        ("gpb", c_int), ("pairs_per_block", c_int), ("slices", c_int),
+        ("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid2_x", C.c_uint), ("grid2_y", C.c_uint), ("workspace_bytes", c_size_t),
+    ]
+
+
+class GnBwdPlan(C.Structure):
+    """pf_gn_bwd_plan"""
+    _fields_ = [
+        ("ppc", c_int), ("chunks", c_int), ("pix_par", c_int), ("bwd_lds_bytes", C.c_uint), ("param_lds_bytes", C.c_uint),
+        ("partial_grid_x", C.c_uint), ("partial_grid_y", C.c_uint), ("finalize_grid_x", C.c_uint),
+        ("apply_grid_x", C.c_uint), ("apply_grid_y", C.c_uint),
+        ("bwd_workspace_bytes", c_size_t), ("param_partial_bytes", c_size_t), ("param_workspace_bytes", c_size_t),
+    ]
+
+
+class LnPlan(C.Structure):
+    """pf_ln_plan"""
+    _fields_ = [("rows_per_wave", c_int), ("grid_x", C.c_uint), ("bwd_parts", c_int)]
+
+
 class AttnBwdDesc(C.Structure):
     """pf_attn_bwd_desc"""
     _fields_ = [
@@ -224,6 +251,9 @@ SIGNATURES = {
     "pf_attention_bwd": (c_int, [C.POINTER(AttnBwdDesc), c_void_p]),
     "pf_attention_bwd_workspace_size": (c_size_t, [C.POINTER(AttnBwdDesc)]),
     "pf_attention_bwd_plan": (c_int, [C.POINTER(AttnBwdDesc), C.POINTER(AttnBwdPlan)]),
+    "pf_groupnorm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(GnPlan)]),
+    "pf_groupnorm_bwd_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, C.POINTER(GnBwdPlan)]),
+    "pf_layernorm_plan": (c_int, [c_long, c_int, C.POINTER(LnPlan)]),
     "pf_layernorm_bwd_parts": (c_int, [c_long]),
     "pf_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_int, c_void_p, c_float, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),

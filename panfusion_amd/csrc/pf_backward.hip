@@ -15,6 +15,7 @@
 //   LayerNorm backward   one row per wavefront, per-block partial sums for gamma / beta (reduced by k_colsum)
 //   GEGLU backward, column sums (bias gradients), gradient normalisation (amax -> power-of-two scale).
 #include "pf_attention_plan.h"
+#include "pf_norm_plan.h"
 #include <algorithm>
 #include <stdlib.h>
 #include <type_traits>
@@ -614,8 +615,6 @@ __global__ void k_attn_delta(const unsigned short* __restrict__ o, const unsigne
 }
 
 // ---- LayerNorm backward -------------------------------------------------------------------------------------------
-constexpr int LN_BWD_MAX_PARTS = 512;
-
 template <typename TI> __device__ __forceinline__ void load8_any(const void* base, long idx, float (&f)[8]) {
     unpack8<TI>(*reinterpret_cast<const u16x8*>(static_cast<const unsigned short*>(base) + idx), f);
 }
@@ -1321,19 +1320,16 @@ extern "C" pf_status pf_attention_bwd(const pf_attn_bwd_desc* d, void* stream) {
     return PF_OK;
 }
 
-extern "C" int pf_layernorm_bwd_parts(long rows) {
-    return static_cast<int>(std::max(1L, std::min<long>(LN_BWD_MAX_PARTS, cdiv(rows, 4))));
-}
-
 extern "C" pf_status pf_layernorm_bwd(const void* x, const float* pe, long pe_rows, int dtype, long rows, int C,
                                       const float* gamma, float eps, const float* dy, const float* dres, float* dx,
                                       float* partials, void* stream) {
-    PF_REQUIRE(x && gamma && dy && dx && partials && rows > 0, "pf_layernorm_bwd: bad arguments");
-    PF_REQUIRE(C > 0 && C % 8 == 0 && C <= 2048, "pf_layernorm_bwd: C=%d must be a multiple of 8, at most 2048", C);
+    PF_REQUIRE(x && gamma && dy && dx && partials, "pf_layernorm_bwd: bad arguments");
+    pf_ln_plan g;
+    if (pf_status bad = plan_layernorm_bwd(rows, C, &g)) return bad;
     PF_REQUIRE(!pe || pe_rows > 0, "pf_layernorm_bwd: pe_rows must be positive");
     PF_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(gamma) && (!pe || aligned16(pe)) && (!dres || aligned16(dres)),
                "pf_layernorm_bwd: pointers must be 16-byte aligned");
-    const int parts = pf_layernorm_bwd_parts(rows);
+    const int parts = g.bwd_parts;
     hipStream_t st = as_stream(stream);
     const dim3 grid(parts), block(256);
     if (dtype == PF_F32) hipLaunchKernelGGL(k_layernorm_bwd<float>, grid, block, 0, st, x, pe, pe_rows, rows, C, gamma, eps, dy, dres, dx, partials, parts);
@@ -1454,46 +1450,28 @@ extern "C" pf_status pf_scale_f32(const float* x, long n, const float* state, in
     return PF_OK;
 }
 
-static int gn_bwd_chunks(int hw, int* pix_per_chunk) {
-    int ppc = 64;
-    while (ppc > 8 && cdiv(hw, ppc) < 16) ppc >>= 1;
-    *pix_per_chunk = ppc;
-    return static_cast<int>(cdiv(hw, ppc));
-}
-
-extern "C" size_t pf_groupnorm_bwd_workspace_size(int n_img, int hw, int groups) {
-    if (n_img <= 0 || hw <= 0 || groups <= 0) return 0;
-    int ppc;
-    const int chunks = gn_bwd_chunks(hw, &ppc);
-    return (static_cast<size_t>(n_img) * chunks * groups * 4 + static_cast<size_t>(n_img) * groups * 4) * sizeof(float);
-}
-
 extern "C" pf_status pf_groupnorm_bwd(const void* x0, int c0, const void* x1, int c1, int dtype, int n_img, int hw, int groups,
                                       float eps, const float* gamma, const float* scale, const float* shift, int act,
                                       const float* dy, const float* dres, float* dx0, float* dx1, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-    PF_REQUIRE(x0 && gamma && scale && shift && dy && dx0 && workspace && n_img > 0 && hw > 0, "pf_groupnorm_bwd: bad arguments");
+    PF_REQUIRE(x0 && gamma && scale && shift && dy && dx0 && workspace, "pf_groupnorm_bwd: bad arguments");
     if (!x1) c1 = 0;
     PF_REQUIRE(c1 == 0 || dx1, "pf_groupnorm_bwd: two sources need two gradient outputs");
-    const int C = c0 + c1;
-    PF_REQUIRE(c0 > 0 && c0 % 8 == 0 && c1 % 8 == 0 && groups > 0 && C % groups == 0, "pf_groupnorm_bwd: channels (%d,%d) must be multiples of 8 and divide into %d groups", c0, c1, groups);
-    PF_REQUIRE(n_img <= 65535, "pf_groupnorm_bwd: at most 65535 images per call");
+    pf_gn_bwd_plan g;
+    if (pf_status bad = plan_groupnorm_bwd(n_img, hw, c0, c1, groups, &g)) return bad;
     PF_REQUIRE(act == 0 || act == 1, "pf_groupnorm_bwd: act must be 0 (none) or 1 (SiLU)");
-    PF_REQUIRE(workspace_bytes >= pf_groupnorm_bwd_workspace_size(n_img, hw, groups), "pf_groupnorm_bwd: workspace too small");
+    PF_REQUIRE(workspace_bytes >= g.bwd_workspace_bytes, "pf_groupnorm_bwd: workspace too small");
     PF_REQUIRE(aligned16(x0) && (!x1 || aligned16(x1)) && aligned16(dy) && aligned16(dx0) && (!dx1 || aligned16(dx1)) && aligned16(gamma) &&
                aligned16(scale) && aligned16(shift) && (!dres || aligned16(dres)) && aligned16(workspace), "pf_groupnorm_bwd: pointers must be 16-byte aligned");
-    int ppc;
-    const int chunks = gn_bwd_chunks(hw, &ppc);
+    const int C = c0 + c1, chunks = g.chunks, ppc = g.ppc;
     float* partial = static_cast<float*>(workspace);
     float* stats = partial + static_cast<size_t>(n_img) * chunks * groups * 4;
-    const int OCT = C / 8, OCTB = OCT < 256 ? OCT : 256, pix_par = 256 / OCTB;
-    const size_t smem = static_cast<size_t>(4) * pix_par * C * sizeof(float);
-    PF_REQUIRE(smem <= 64 * 1024, "pf_groupnorm_bwd: %d channels exceed the 64 KiB staging buffer", C);
+    const size_t smem = g.bwd_lds_bytes;
     hipStream_t st = as_stream(stream);
-    const dim3 g1(chunks, n_img), g3(cdiv(static_cast<long>(hw) * OCT, 256), n_img), block(256);
+    const dim3 g1(g.partial_grid_x, g.partial_grid_y), g3(g.apply_grid_x, g.apply_grid_y), block(256);
 #define PF_GNB(TI) do {                                                                                                     \
         hipLaunchKernelGGL(k_gn_bwd_partial<TI>, g1, block, smem, st, x0, c0, x1, c1, hw, groups, ppc, gamma, scale, shift, act, dy, partial); \
-        hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(n_img), block, 0, st, partial, chunks, groups, C, hw, eps, stats);             \
+        hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(g.finalize_grid_x), block, 0, st, partial, chunks, groups, C, hw, eps, stats); \
         hipLaunchKernelGGL(k_gn_bwd_apply<TI>, g3, block, 0, st, x0, c0, x1, c1, hw, groups, gamma, scale, shift, act, dy, dres, stats, dx0, dx1); \
     } while (0)
     if (dtype == PF_F32) PF_GNB(float);
@@ -1505,36 +1483,25 @@ extern "C" pf_status pf_groupnorm_bwd(const void* x0, int c0, const void* x1, in
     return PF_OK;
 }
 
-extern "C" size_t pf_groupnorm_param_grads_workspace_size(int n_img, int hw, int C) {
-    if (n_img <= 0 || hw <= 0 || C <= 0) return 0;
-    int ppc;
-    const long rows = static_cast<long>(n_img) * gn_bwd_chunks(hw, &ppc);
-    return static_cast<size_t>(rows) * 2 * C * sizeof(float) + pf_colsum_workspace_size(rows, 2 * C);
-}
-
 extern "C" pf_status pf_groupnorm_param_grads(const void* x0, int c0, const void* x1, int c1, int dtype, int n_img, int hw,
                                               const float* scale, const float* shift, const float* unit_scale, const float* unit_shift,
                                               int act, const float* dy, float* dgamma_dbeta, void* workspace, size_t workspace_bytes,
                                               void* stream) {
-    PF_REQUIRE(x0 && scale && shift && unit_scale && unit_shift && dy && dgamma_dbeta && workspace && n_img > 0 && hw > 0,
+    PF_REQUIRE(x0 && scale && shift && unit_scale && unit_shift && dy && dgamma_dbeta && workspace,
                "pf_groupnorm_param_grads: bad arguments");
     if (!x1) c1 = 0;
-    const int C = c0 + c1;
-    PF_REQUIRE(c0 > 0 && c0 % 8 == 0 && c1 % 8 == 0, "pf_groupnorm_param_grads: channels (%d,%d) must be multiples of 8", c0, c1);
-    PF_REQUIRE(n_img <= 65535, "pf_groupnorm_param_grads: at most 65535 images per call");
+    pf_gn_bwd_plan g;
+    if (pf_status bad = plan_groupnorm_param_grads(n_img, hw, c0, c1, &g)) return bad;
     PF_REQUIRE(act == 0 || act == 1, "pf_groupnorm_param_grads: act must be 0 (none) or 1 (SiLU)");
-    PF_REQUIRE(workspace_bytes >= pf_groupnorm_param_grads_workspace_size(n_img, hw, C), "pf_groupnorm_param_grads: workspace too small");
+    PF_REQUIRE(workspace_bytes >= g.param_workspace_bytes, "pf_groupnorm_param_grads: workspace too small");
     PF_REQUIRE(aligned16(x0) && (!x1 || aligned16(x1)) && aligned16(dy) && aligned16(scale) && aligned16(shift) && aligned16(unit_scale) &&
                aligned16(unit_shift) && aligned16(workspace), "pf_groupnorm_param_grads: pointers must be 16-byte aligned");
-    int ppc;
-    const int chunks = gn_bwd_chunks(hw, &ppc);
-    const long rows = static_cast<long>(n_img) * chunks;
+    const int C = c0 + c1, ppc = g.ppc;
+    const long rows = static_cast<long>(n_img) * g.chunks;
     float* partial = static_cast<float*>(workspace);
-    const int OCT = C / 8, OCTB = OCT < 256 ? OCT : 256, pix_par = 256 / OCTB;
-    const size_t smem = static_cast<size_t>(2) * pix_par * C * sizeof(float);
-    PF_REQUIRE(smem <= 64 * 1024, "pf_groupnorm_param_grads: %d channels exceed the 64 KiB staging buffer", C);
+    const size_t smem = g.param_lds_bytes;
     hipStream_t st = as_stream(stream);
-    const dim3 grid(chunks, n_img), block(256);
+    const dim3 grid(g.partial_grid_x, g.partial_grid_y), block(256);
 #define PF_GNP(TI) hipLaunchKernelGGL(k_gn_param_partial<TI>, grid, block, smem, st, x0, c0, x1, c1, hw, ppc, scale, shift, unit_scale, unit_shift, act, dy, partial)
     if (dtype == PF_F32) PF_GNP(float);
     else if (dtype == PF_F16) PF_GNP(F16);
@@ -1542,7 +1509,7 @@ extern "C" pf_status pf_groupnorm_param_grads(const void* x0, int c0, const void
     else PF_REQUIRE(false, "pf_groupnorm_param_grads: unsupported dtype %d", dtype);
 #undef PF_GNP
     PF_CHECK_LAUNCH("pf_groupnorm_param_grads");
-    const size_t used = static_cast<size_t>(rows) * 2 * C * sizeof(float);
+    const size_t used = g.param_partial_bytes;
     return pf_colsum(partial, PF_F32, rows, 2 * C, 2 * C, dgamma_dbeta, reinterpret_cast<char*>(workspace) + used, workspace_bytes - used, stream);
 }
 

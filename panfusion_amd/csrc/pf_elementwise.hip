@@ -10,7 +10,7 @@
 // models/pano/MVGenModel.py:98-294; models/modules/transformer.py:8-38,151-162;
 // utils/pano.py:74-105; models/pano/PanoGenerator.py:253-269; DDIMScheduler.step /
 // DPMSolverMultistepScheduler.step (models/pano/PanFusion.py:159-162).
-#include "pf_common.h"
+#include "pf_norm_plan.h"
 #include <stdlib.h>
 #include <math.h>
 #include <algorithm>
@@ -128,7 +128,6 @@ __global__ __launch_bounds__(256) void k_gn_partial(const typename In8<TI>::elem
 // grid (image, group block of GPB groups): 256 / GPB lanes share a group (4 independent loads in flight each),
 // combined in a fixed order.  (Round 3: one block per image walked the chunks serially -- 24 us per launch on the
 // 2-image panorama branch, 0.9 ms per step in 122 launches.)
-constexpr int GN_GPB = 8;
 __global__ __launch_bounds__(256) void k_gn_finalize(const float* __restrict__ partial, int nchunks, int groups, int C,
                               int hw, float eps, const float* __restrict__ gamma,
                               const float* __restrict__ beta, float* __restrict__ scale,
@@ -1206,24 +1205,6 @@ using namespace pf;
         else { pf::set_error("%s: dtype must be PF_BF16, PF_F16 or PF_F32", name); return PF_ERR_ARG; } \
     } while (0)
 
-// pixels per statistics chunk: ~2048 blocks in flight, 8..64 pixels each, at most 256 chunks per image
-static int gn_pixels_per_chunk(int n_img, int hw) {
-    long ppc = static_cast<long>(n_img) * hw / 2048;
-    if (ppc > 64) ppc = 64;
-    if (ppc < 8) ppc = 8;
-    const long floor_ppc = cdiv(hw, 256);
-    if (ppc < floor_ppc) ppc = floor_ppc;
-    if (ppc > hw) ppc = hw;
-    return static_cast<int>(ppc);
-}
-
-extern "C" size_t pf_groupnorm_workspace_size(int n_img, int hw, int C) {
-    (void)C;
-    const int ppc = gn_pixels_per_chunk(n_img, hw);
-    const long nchunks = cdiv(hw, ppc);
-    return static_cast<size_t>(n_img) * nchunks * 64 * 2 * sizeof(float);   // up to 64 groups
-}
-
 static pf_status groupnorm_stats_impl(const void* x0, int c0, const void* x1, int c1, int dtype,
                                       int n_img, int hw, int groups, float eps, const float* gamma,
                                       const float* beta, float* scale, float* shift, void* workspace,
@@ -1245,36 +1226,29 @@ static pf_status groupnorm_stats_impl(const void* x0, int c0, const void* x1, in
                                       int n_img, int hw, int groups, float eps, const float* gamma,
                                       const float* beta, float* scale, float* shift, void* workspace,
                                       size_t ws_bytes, void* stream, int wimg, int wrap) {
-    const int C = c0 + (x1 ? c1 : 0);
     if (!x1) c1 = 0;
     PF_REQUIRE(x0 && gamma && beta && scale && shift && workspace, "pf_groupnorm_stats: null pointer");
-    PF_REQUIRE(n_img > 0 && hw > 0 && groups > 0 && groups <= 64, "pf_groupnorm_stats: bad sizes");
-    PF_REQUIRE(C % 8 == 0 && c0 % 8 == 0 && C % groups == 0, "pf_groupnorm_stats: C=%d must be a multiple of 8 and of groups=%d", C, groups);
+    pf_gn_plan g;
+    if (pf_status bad = plan_groupnorm(n_img, hw, c0, c1, groups, dtype, 0, 0, &g)) return bad;
     PF_REQUIRE(aligned16(x0) && (!x1 || aligned16(x1)), "pf_groupnorm_stats: inputs must be 16-byte aligned");
-    PF_REQUIRE(dtype != PF_F32 || (c0 % 4 == 0 && c1 % 4 == 0), "pf_groupnorm_stats: fp32 sources need c0, c1 %% 4 == 0");
-    PF_REQUIRE(ws_bytes >= pf_groupnorm_workspace_size(n_img, hw, C), "pf_groupnorm_stats: workspace too small");
+    PF_REQUIRE(ws_bytes >= g.workspace_bytes, "pf_groupnorm_stats: workspace too small");
     hipStream_t st = as_stream(stream);
+    const int C = c0 + c1;
     const int hw_counted = wrap > 0 ? hw / wimg * (wimg + 2 * wrap) : hw;         // pixels of the virtually padded tensor
-    static const long direct_max = getenv("PF_GN_DIRECT_MAX") ? atol(getenv("PF_GN_DIRECT_MAX")) : 32768;   // elements per (image, group); 0 = off (A/B)
-    if (static_cast<long>(hw) * (C / groups) <= direct_max && static_cast<long>(n_img) * hw * C <= (4L << 20)) {
+    if (g.arm == PF_GN_DIRECT) {
         PF_DISPATCH_IN(dtype, "pf_groupnorm_stats",
-            hipLaunchKernelGGL(k_gn_stats_direct<TI>, dim3(n_img, groups), dim3(256), 0, st,
+            hipLaunchKernelGGL(k_gn_stats_direct<TI>, dim3(g.grid_x, g.grid_y), dim3(256), 0, st,
                                static_cast<const In8<TI>::elem*>(x0), c0, static_cast<const In8<TI>::elem*>(x1), c1,
                                hw, groups, hw_counted, eps, gamma, beta, scale, shift, wimg, wrap));
         PF_CHECK_LAUNCH("pf_groupnorm_stats (direct)");
         return PF_OK;
     }
-    const int ppc = gn_pixels_per_chunk(n_img, hw);
-    const int nchunks = static_cast<int>(cdiv(hw, ppc));
-    const int OCT = C / 8, OCTB = OCT < 256 ? OCT : 256, pix_par = 256 / OCTB;
-    const size_t smem = static_cast<size_t>(2) * pix_par * C * sizeof(float);
-    PF_REQUIRE(smem <= 64 * 1024, "pf_groupnorm_stats: C=%d too large", C);
     float* partial = static_cast<float*>(workspace);
     PF_DISPATCH_IN(dtype, "pf_groupnorm_stats",
-        hipLaunchKernelGGL(k_gn_partial<TI>, dim3(nchunks, n_img), dim3(256), smem, st,
+        hipLaunchKernelGGL(k_gn_partial<TI>, dim3(g.grid_x, g.grid_y), dim3(256), g.lds_bytes, st,
                            static_cast<const In8<TI>::elem*>(x0), c0, static_cast<const In8<TI>::elem*>(x1), c1,
-                           hw, groups, ppc, partial, wimg, wrap));
-    hipLaunchKernelGGL(k_gn_finalize, dim3(n_img, cdiv(groups, GN_GPB)), dim3(256), 0, st, partial, nchunks, groups, C, hw_counted, eps,
+                           hw, groups, g.ppc, partial, wimg, wrap));
+    hipLaunchKernelGGL(k_gn_finalize, dim3(g.grid2_x, g.grid2_y), dim3(256), 0, st, partial, g.nchunks, groups, C, hw_counted, eps,
                        gamma, beta, scale, shift);
     PF_CHECK_LAUNCH("pf_groupnorm_stats");
     return PF_OK;
@@ -1284,19 +1258,11 @@ extern "C" pf_status pf_groupnorm_from_partials(const float* part0, int c0, int 
                                                 int n_img, int hw, int groups, float eps, const float* gamma,
                                                 const float* beta, float* scale, float* shift, void* stream) {
     if (!part1) { c1 = 0; rows1 = rows0; }
-    const int C = c0 + c1;
     PF_REQUIRE(part0 && gamma && beta && scale && shift, "pf_groupnorm_from_partials: null pointer");
-    PF_REQUIRE(n_img > 0 && hw > 0 && groups > 0 && groups <= 64 && C % groups == 0 && c0 > 0,
-               "pf_groupnorm_from_partials: bad sizes");
-    PF_REQUIRE(rows0 > 0 && rows1 > 0 && hw % rows0 == 0 && hw % rows1 == 0,
-               "pf_groupnorm_from_partials: an image (%d rows) must be whole runs of %d / %d rows", hw, rows0, rows1);
-    PF_REQUIRE((C / groups) % 2 == 0 && c0 % 2 == 0 && c1 % 2 == 0, "pf_groupnorm_from_partials: groups and sources must hold even numbers of channels (moments are per column pair)");
-    const int ppi = std::max(hw / rows0, hw / rows1);
-    int gpb = ppi <= 32 ? 8 : ppi <= 128 ? 4 : ppi <= 512 ? 2 : 1;       // fewer groups per block = more slices walking the parts
-    while (gpb > 1 && gpb * (C / groups) / 2 > 512) gpb >>= 1;
-    PF_REQUIRE(gpb * (C / groups) / 2 <= 512, "pf_groupnorm_from_partials: C=%d too large for %d groups", C, groups);
-    hipLaunchKernelGGL(k_gn_finalize_cols, dim3(n_img, cdiv(groups, gpb)), dim3(256), 0, as_stream(stream),
-                       part0, c0, hw / rows0, part1, c1, hw / rows1, groups, gpb, hw, eps, gamma, beta, scale, shift);
+    pf_gn_plan g;
+    if (pf_status bad = plan_groupnorm_partials(n_img, hw, c0, rows0, c1, rows1, groups, &g)) return bad;
+    hipLaunchKernelGGL(k_gn_finalize_cols, dim3(g.grid_x, g.grid_y), dim3(256), 0, as_stream(stream),
+                       part0, c0, hw / rows0, part1, c1, hw / rows1, groups, g.gpb, hw, eps, gamma, beta, scale, shift);
     PF_CHECK_LAUNCH("pf_groupnorm_from_partials");
     return PF_OK;
 }
@@ -1355,24 +1321,20 @@ static pf_status scale_shift_act_impl(const void* x0, int c0, const void* x1, in
 extern "C" pf_status pf_layernorm(const void* x, const float* pe, long pe_rows, int dtype, long rows,
                                   int C, const float* gamma, const float* beta, float eps, int out_dtype, void* y,
                                   void* stream) {
-    PF_REQUIRE(x && gamma && beta && y && rows > 0, "pf_layernorm: bad arguments");
-    PF_REQUIRE(C % 8 == 0 && C <= 2048, "pf_layernorm: C=%d must be a multiple of 8 and <= 2048", C);
+    PF_REQUIRE(x && gamma && beta && y, "pf_layernorm: bad arguments");
+    pf_ln_plan g;
+    if (pf_status bad = plan_layernorm(rows, C, &g)) return bad;
     PF_REQUIRE(!pe || pe_rows > 0, "pf_layernorm: pe_rows must be > 0 with pe");
     PF_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && (!pe || aligned16(pe)),
                "pf_layernorm: pointers must be 16-byte aligned");
     PF_REQUIRE(dtype == PF_F32 || dtype == out_dtype, "pf_layernorm: a 16-bit input must have the output's type");
     hipStream_t st = as_stream(stream);
     unsigned short* yo = static_cast<unsigned short*>(y);
-#define PF_LN(TI, T) do {                                                                                                \
-        if (C <= 512 && rows >= 4096)      /* narrow rows: 4 rows per wavefront in flight */                             \
-            hipLaunchKernelGGL((k_layernorm<TI, T, 4>), dim3(cdiv(rows, 16)), dim3(256), 0, st,                          \
-                               static_cast<const In8<TI>::elem*>(x), pe, pe_rows, rows, C, gamma, beta, eps, yo);        \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_layernorm<TI, T, 1>), dim3(cdiv(rows, 4)), dim3(256), 0, st,                           \
-                               static_cast<const In8<TI>::elem*>(x), pe, pe_rows, rows, C, gamma, beta, eps, yo);        \
-    } while (0)
+#define PF_LN(TI, T, ROWS) hipLaunchKernelGGL((k_layernorm<TI, T, ROWS>), dim3(g.grid_x), dim3(256), 0, st,                \
+                                              static_cast<const In8<TI>::elem*>(x), pe, pe_rows, rows, C, gamma, beta, eps, yo)
     PF_DISPATCH_16(out_dtype, "pf_layernorm",
-        if (dtype == PF_F32) PF_LN(F32In, T); else PF_LN(T, T));
+        if (dtype == PF_F32) { if (g.rows_per_wave == 4) PF_LN(F32In, T, 4); else PF_LN(F32In, T, 1); }
+        else { if (g.rows_per_wave == 4) PF_LN(T, T, 4); else PF_LN(T, T, 1); });
 #undef PF_LN
     PF_CHECK_LAUNCH("pf_layernorm");
     return PF_OK;

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PF_BF16, PF_F16, PF_F32, AttnBwdDesc, AttnBwdPlan, AttnDesc, AttnPlan, ConvDesc, ConvPlan, LinearWsDesc, LwsPlan, check
+from ._lib import (PF_BF16, PF_F16, PF_F32, PF_GN_FROM_PARTIALS, AttnBwdDesc, AttnBwdPlan, AttnDesc, AttnPlan, ConvDesc, ConvPlan, GnPlan,
+                   LinearWsDesc, LwsPlan, check)
 
 _DT = {torch.bfloat16: PF_BF16, torch.float16: PF_F16, torch.float32: PF_F32}
 
@@ -210,6 +211,22 @@ def carry(dst, src):
     return dst
 
 
+_GN_PLANS = _PlanCache()         # the arguments of pf_groupnorm_plan -> its GnPlan (nothing the plan reads changes inside a process)
+
+
+def _gn_plan(key):
+    """pf_groupnorm_plan of (n_img, hw, c0, c1, groups, dtype, rows0, rows1), asked once per problem; a refused problem raises."""
+    plans = _GN_PLANS.plans
+    g = plans.get(key)
+    if g is None:
+        g = GnPlan()
+        check(_lib.lib().pf_groupnorm_plan(*key, C.byref(g)), "pf_groupnorm_plan")
+        if len(plans) >= _GN_PLANS.LIMIT:
+            plans.pop(next(iter(plans)))
+        plans[key] = g
+    return g
+
+
 def groupnorm_scale_shift(x0, x1, n_img, hw, groups, eps, gamma, beta, ws=None, wrap=None):
     """x0 [n, hw, c0] (+ x1 [n, hw, c1] concatenated along channels) -> (scale, shift) [n, C] fp32.
     wrap = (image width, p): statistics of the tensor as if its width had been padded circularly by p columns (pad_pano).
@@ -222,27 +239,26 @@ def groupnorm_scale_shift(x0, x1, n_img, hw, groups, eps, gamma, beta, ws=None, 
     shift = torch.empty_like(scale)
     st0 = getattr(x0, "_pf_gn", None)
     st1 = getattr(x1, "_pf_gn", None) if x1 is not None else None
-    if wrap is not None and wrap[1] > 0:
-        nbytes = _lib.lib().pf_groupnorm_workspace_size(n_img, hw, Cc)
-        ws = torch.empty(nbytes, device=x0.device, dtype=torch.uint8)
-        check(_lib.lib().pf_groupnorm_stats_wrap(_p(x0), c0, _p(x1), c1, dt(x0), n_img, hw // wrap[0], wrap[0], wrap[1], groups, eps,
-                                                 _p(gamma), _p(beta), _p(scale), _p(shift), _p(ws), ws.numel(), _stream()),
-              "pf_groupnorm_stats_wrap")
-        return scale, shift
-    usable = st0 is not None and (x1 is None or st1 is not None) and (Cc // groups) % 2 == 0 and c0 % 2 == 0
-    if usable and (hw % st0[1] or (st1 is not None and hw % st1[1])):
-        usable = False                # (a linear layer's moment runs need not respect this consumer's image boundaries)
-    if usable:
+    wrapped = wrap is not None and wrap[1] > 0
+    offered = not wrapped and st0 is not None and (x1 is None or st1 is not None)
+    # whether offered moments can serve is the library's decision (a linear layer's moment runs need not respect this consumer's
+    # image boundaries, groups may hold odd numbers of channels): where they cannot, the plan is that of the statistics pass
+    g = _gn_plan((n_img, hw, c0, c1, groups, dt(x0), st0[1] if offered else 0, st1[1] if offered and st1 else 0))
+    if g.arm == PF_GN_FROM_PARTIALS:
         check(_lib.lib().pf_groupnorm_from_partials(_p(st0[0]), c0, st0[1], _p(st1[0]) if st1 else None, c1,
                                                     st1[1] if st1 else st0[1], n_img, hw, groups, eps, _p(gamma), _p(beta),
                                                     _p(scale), _p(shift), _stream()), "pf_groupnorm_from_partials")
         return scale, shift
-    nbytes = _lib.lib().pf_groupnorm_workspace_size(n_img, hw, Cc)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, device=x0.device, dtype=torch.uint8)
-    check(_lib.lib().pf_groupnorm_stats(_p(x0), c0, _p(x1), c1, dt(x0), n_img, hw, groups, eps, _p(gamma),
-                                        _p(beta), _p(scale), _p(shift), _p(ws), ws.numel(), _stream()),
-          "pf_groupnorm_stats")
+    if wrapped or ws is None or ws.numel() < g.workspace_bytes:
+        ws = torch.empty(g.workspace_bytes, device=x0.device, dtype=torch.uint8)
+    if wrapped:
+        check(_lib.lib().pf_groupnorm_stats_wrap(_p(x0), c0, _p(x1), c1, dt(x0), n_img, hw // wrap[0], wrap[0], wrap[1], groups, eps,
+                                                 _p(gamma), _p(beta), _p(scale), _p(shift), _p(ws), ws.numel(), _stream()),
+              "pf_groupnorm_stats_wrap")
+    else:
+        check(_lib.lib().pf_groupnorm_stats(_p(x0), c0, _p(x1), c1, dt(x0), n_img, hw, groups, eps, _p(gamma),
+                                            _p(beta), _p(scale), _p(shift), _p(ws), ws.numel(), _stream()),
+              "pf_groupnorm_stats")
     return scale, shift
 
 

@@ -6,11 +6,14 @@ exercise the HOST logic of the product -- layer sequencing, skip/pad/crop bookke
 packing, sharding and collectives over gloo -- without a GPU.  It is not a fallback: the product
 never imports it, and nothing here is measured.
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from oracle import geometry as G
+from panfusion_amd import _lib
 
 TRACE = None
 
@@ -100,9 +103,13 @@ def groupnorm_scale_shift(x0, x1, n_img, hw, groups, eps, gamma, beta, ws=None, 
     st1 = getattr(x1, "_pf_gn", None) if x1 is not None else None
     c0 = x0.shape[-1]
     c1 = x1.shape[-1] if x1 is not None else 0
-    usable = st0 is not None and (x1 is None or st1 is not None) and ((c0 + c1) // groups) % 2 == 0 and c0 % 2 == 0
-    if usable and (hw % st0[1] or (st1 is not None and hw % st1[1])):
-        usable = False
+    usable = st0 is not None and (x1 is None or st1 is not None)
+    if usable:                                    # whether offered moments serve is the library's rule (host arithmetic, no GPU), as in ops.py
+        # (the status is not looked at: a problem the library refuses -- this fake also serves widths that are no multiple of 8 --
+        # has an all-zero plan, arm 0, and takes the pass over the tensor below)
+        g = _lib.GnPlan()
+        _lib.lib().pf_groupnorm_plan(n_img, hw, c0, c1, groups, dt(x0), st0[1], st1[1] if st1 else 0, ctypes.byref(g))
+        usable = g.arm == _lib.PF_GN_FROM_PARTIALS
     if usable:
         # the product's path: per-column-PAIR moments over runs of `rows` output rows, as pf_conv_gemm's epilogue leaves them
         GN_FROM_PARTIALS[0] += 1

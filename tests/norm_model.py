@@ -132,7 +132,9 @@ def partials_gpb(hw, rows0, rows1, C, groups):
 
 
 def partials_usable(hw, rows0, rows1, c0, C, groups):
-    return (C // groups) % 2 == 0 and c0 % 2 == 0 and hw % rows0 == 0 and hw % rows1 == 0
+    """Even channels per group and source, images that are whole runs of both sources, and at most 512 column pairs in one group (what
+    a block of k_gn_finalize_cols holds at one group per block)."""
+    return (C // groups) % 2 == 0 and c0 % 2 == 0 and hw % rows0 == 0 and hw % rows1 == 0 and (C // groups) // 2 <= 512
 
 
 def ln_rows_per_wave(rows, C):

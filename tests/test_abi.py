@@ -42,7 +42,7 @@ def test_struct_layouts_match_header(tmp_path):
     import subprocess
     structs = {"pf_conv_desc": _lib.ConvDesc, "pf_attn_desc": _lib.AttnDesc, "pf_attn_bwd_desc": _lib.AttnBwdDesc,
                "pf_linear_ws_desc": _lib.LinearWsDesc, "pf_conv_plan": _lib.ConvPlan, "pf_attn_plan": _lib.AttnPlan, "pf_attn_bwd_plan": _lib.AttnBwdPlan,
-               "pf_lws_plan": _lib.LwsPlan}
+               "pf_lws_plan": _lib.LwsPlan, "pf_gn_plan": _lib.GnPlan, "pf_gn_bwd_plan": _lib.GnBwdPlan, "pf_ln_plan": _lib.LnPlan}
     lines = []
     for cname, cls in structs.items():
         lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))

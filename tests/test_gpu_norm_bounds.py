@@ -214,3 +214,68 @@ def test_layernorm(i, types):
         print("RATIO layernorm rows/wave %d %-24s %s->%s pe%d L %2d  worst |err| / bound %.3f"
               % (c.rpw, c.name, M.DT_ID[tin], M.DT_ID[tout], with_pe, c.L, ratio(y.cpu(), ref.y, bound)))
         M.assert_within(name, y.cpu(), ref.y, bound)
+
+
+# ------------------------------------------------------------------------------------------------ the plans' workspaces
+GUARD = 4096             # bytes behind the workspace, filled with 0xA5
+
+
+def test_launches_stay_inside_the_workspace_their_plan_states():
+    """The launch is handed exactly the plan's workspace_bytes with a filled guard band behind: the band is untouched, the results equal
+    those of a call with a generous workspace bit for bit, and a workspace one byte short is PF_ERR_ARG `workspace too small` before
+    anything is launched (the outputs keep their NaN fill).  The smallest two-stage statistics case; a backward whose pixels per chunk
+    have halved to 8, and its parameter gradients."""
+    import ctypes as C
+
+    from panfusion_amd import _lib
+    o, lib = ops(), _lib.lib()
+    p, st = o._p, o._stream
+
+    def thrice(name, nbytes, outputs, launch):
+        """launch(workspace pointer, bytes) -> status, run with a generous, the exact and a short workspace."""
+        results = []
+        for extra in (1 << 20, 0):
+            ws = torch.full((nbytes + extra + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+            for t in outputs:
+                t.fill_(float("nan"))
+            assert launch(p(ws), nbytes + extra) == 0, (name, lib.pf_last_error_string())
+            torch.cuda.synchronize()
+            assert bool((ws[nbytes + extra:] == 0xA5).all()), "%s: wrote behind its workspace of %d bytes" % (name, nbytes + extra)
+            assert all(bool(torch.isfinite(t).all()) for t in outputs), name
+            results.append([t.clone() for t in outputs])
+        for a, b in zip(*results):
+            assert bool((bits(a) == bits(b)).all()), "%s: the exact workspace changes the result" % name
+        for t in outputs:
+            t.fill_(float("nan"))
+        assert launch(p(ws), nbytes - 1) == 1 and (b"%s: workspace too small" % name.encode()) in lib.pf_last_error_string()
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(t).all()) for t in outputs), "%s: launched with a short workspace" % name
+
+    # ---- statistics: n = 1, hw = 4099, C = 320, fp16 (two-stage, 17 pixels per chunk, a ragged last chunk)
+    c = next(k for k in M.GN_CASES if k.name == "two_stage-1x4099x320-g32")
+    x = M.gn_inputs(c, torch.float16, seed=11)
+    g = _lib.GnPlan()
+    assert lib.pf_groupnorm_plan(c.n, c.hw, c.c0, 0, c.groups, _lib.PF_F16, 0, 0, C.byref(g)) == 0
+    assert (g.arm, g.ppc, g.nchunks) == (_lib.PF_GN_TWO_STAGE, 17, 242) and g.workspace_bytes == 242 * 512
+    x0, gam, bet = dev_view(x.x0), x.gamma.to(DEV), x.beta.to(DEV)
+    sc, sh = torch.empty(c.n, c.c0, device=DEV), torch.empty(c.n, c.c0, device=DEV)
+    thrice("pf_groupnorm_stats", g.workspace_bytes, (sc, sh),
+           lambda ws, nb: lib.pf_groupnorm_stats(p(x0), c.c0, None, 0, _lib.PF_F16, c.n, c.hw, c.groups, 1e-5, p(gam), p(bet), p(sc), p(sh), ws, nb, st()))
+    # ---- backward and parameter gradients: n = 2, hw = 130, C = 64, 32 groups (17 chunks of 8 pixels, the last of 2), fp32 dy
+    n, hw, Cc, groups = 2, 130, 64, 32
+    b = _lib.GnBwdPlan()
+    assert lib.pf_groupnorm_bwd_plan(n, hw, Cc, 0, groups, C.byref(b)) == 0 and (b.ppc, b.chunks) == (8, 17)
+    gen = torch.Generator().manual_seed(77)
+    xb = dev_view((torch.randn(n, hw, Cc, generator=gen) * 2 + 0.5).half())
+    dy = dev_view(torch.randn(n, hw, Cc, generator=gen))
+    gam, bet = (torch.randn(Cc, generator=gen) * 0.2 + 1).to(DEV), (torch.randn(Cc, generator=gen) * 0.1).to(DEV)
+    sc, sh = o.groupnorm_scale_shift(xb, None, n, hw, groups, 1e-5, gam, bet)
+    usc, ush = o.groupnorm_scale_shift(xb, None, n, hw, groups, 1e-5, torch.ones_like(gam), torch.zeros_like(bet))
+    dx = torch.empty(n, hw, Cc, device=DEV)
+    thrice("pf_groupnorm_bwd", b.bwd_workspace_bytes, (dx,),
+           lambda ws, nb: lib.pf_groupnorm_bwd(p(xb), Cc, None, 0, _lib.PF_F16, n, hw, groups, 1e-5, p(gam), p(sc), p(sh), 1, p(dy), None,
+                                               p(dx), None, ws, nb, st()))
+    dgb = torch.empty(2 * Cc, device=DEV)
+    thrice("pf_groupnorm_param_grads", b.param_workspace_bytes, (dgb,),
+           lambda ws, nb: lib.pf_groupnorm_param_grads(p(xb), Cc, None, 0, _lib.PF_F16, n, hw, p(sc), p(sh), p(usc), p(ush), 1, p(dy), p(dgb),
+                                                       ws, nb, st()))

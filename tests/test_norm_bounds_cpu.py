@@ -43,6 +43,66 @@ def test_case_tables_reach_the_arms():
     assert len(M.APPLY_COMBOS) == 13
 
 
+def test_the_restated_dispatch_is_the_librarys():
+    """norm_model restates the host dispatch by hand, and the chain lengths L of every bound come from that restatement.  Held against the
+    library's own plans (host arithmetic, no GPU) -- arm, ppc, pix_par, gpb, slices, usable, rows per wave -- on every case of the three
+    tables and on the whole grid of tests/norm_plan_grid.py: a dispatch constant that moves in the library moves this."""
+    import ctypes as C
+
+    import norm_plan_grid as G
+    from panfusion_amd import _lib
+    lib = _lib.lib()
+    ARM = {_lib.PF_GN_DIRECT: "direct", _lib.PF_GN_TWO_STAGE: "two_stage"}
+
+    def stats(n, hw, c0, c1, groups, dtype=_lib.PF_F16, rows0=0, rows1=0):
+        g = _lib.GnPlan()
+        return lib.pf_groupnorm_plan(n, hw, c0, c1, groups, dtype, rows0, rows1, C.byref(g)), g
+
+    def check_stats(g, n, hw, Cc, groups, what):
+        assert ARM[g.arm] == M.gn_arm(n, hw, Cc, groups), what
+        if g.arm == _lib.PF_GN_TWO_STAGE:
+            assert (g.ppc, g.pix_par) == (M.gn_ppc(n, hw), M.gn_pix_par(Cc)), what
+
+    def check_partials(g, n, hw, c0, rows0, c1, rows1, groups, what):
+        usable = M.partials_usable(hw, rows0, rows1, c0, c0 + c1, groups)
+        assert (g.arm == _lib.PF_GN_FROM_PARTIALS) == usable and g.partials_refused == (not usable), what
+        if usable:
+            c = M.part_case("", n, hw, c0, rows0, c1, rows1 if c1 else 0, groups)
+            assert (g.gpb, g.pairs_per_block, g.slices) == (c.gpb, c.npairs, c.slices), what
+        else:
+            check_stats(g, n, hw, c0 + c1, groups, what)
+
+    for c in M.GN_CASES:
+        status, g = stats(c.n, c.hw, c.c0, c.c1, c.groups)
+        assert status == 0 and ARM[g.arm] == c.arm, c.name
+        check_stats(g, c.n, c.hw, c.c0 + c.c1, c.groups, c.name)
+        assert c.L == (M.cdiv(c.hw * ((c.c0 + c.c1) // c.groups), 256) + 6 if c.arm == "direct" else M.cdiv(g.ppc, g.pix_par) + g.pix_par * ((c.c0 + c.c1) // c.groups)), c.name
+    for c in M.PART_CASES:
+        status, g = stats(c.n, c.hw, c.c0, c.c1, c.groups, _lib.PF_F32, c.rows0, c.rows1 if c.c1 else 0)
+        assert status == 0 and (g.arm == _lib.PF_GN_FROM_PARTIALS) == c.usable and (g.gpb, g.slices) == (c.gpb, c.slices), c.name
+        check_partials(g, c.n, c.hw, c.c0, c.rows0, c.c1, c.rows1, c.groups, c.name)
+    for c in M.LN_CASES:
+        g = _lib.LnPlan()
+        assert lib.pf_layernorm_plan(c.rows, c.C, C.byref(g)) == 0 and g.rows_per_wave == c.rpw == M.ln_rows_per_wave(c.rows, c.C), c.name
+    seen = dict(stats=0, partials=0, ln=0)
+    for p in G.gn_problems():
+        status, g = stats(p["n"], p["hw"], p["c0"], p["c1"], p["groups"], p["dtype"], p["rows0"], p["rows1"])
+        if status != 0:                                   # (the model has no notion of a refused problem)
+            continue
+        if p["rows0"] and (p["rows1"] or not p["c1"]):
+            check_partials(g, p["n"], p["hw"], p["c0"], p["rows0"], p["c1"], p["rows1"] or p["rows0"], p["groups"], p)
+            seen["partials"] += 1
+        else:
+            check_stats(g, p["n"], p["hw"], p["c0"] + p["c1"], p["groups"], p)
+            seen["stats"] += 1
+    for p in G.ln_problems():
+        g = _lib.LnPlan()
+        if lib.pf_layernorm_plan(p["rows"], p["C"], C.byref(g)) == 0:
+            assert g.rows_per_wave == M.ln_rows_per_wave(p["rows"], p["C"]), p
+            seen["ln"] += 1
+    assert seen["stats"] >= 60 and seen["partials"] >= 25 and seen["ln"] >= 35, seen
+
+
 # ------------------------------------------------------------------------------------------------ the emulation inside the bounds
 def gn_check(name, sc, sh, ref, c, x):
     dS, dH = M.gn_stat_bounds(ref, c.L, x.gamma, x.beta)
