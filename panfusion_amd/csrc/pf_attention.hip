@@ -283,12 +283,6 @@ __global__ __launch_bounds__(256, OCC) void k_attention_lds(const AttnParams p) 
     // computed once + a per-tile SCALAR offset: no 64-bit vector pointer arithmetic per key tile (four v_lshl_add_u64 and eight
     // address registers in the global-load form, in a kernel bound by each wave's instruction issue).  -DPF_ATTN_BUFLOAD=0: A/B build.
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi_ = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi_) << 32));
-    };
     // (the launcher checks that the slices fit 32-bit offsets; the register-pipelined EPA form measured 3-5 % SLOWER with it on its
     // view-query direction and keeps the global loads)
     constexpr bool bufload = PF_ATTN_BUFLOAD != 0 && !PIPE;
@@ -728,12 +722,6 @@ __global__ __launch_bounds__(512, 1) void k_attention_pp(const AttnParams p) {
 
     // ---- LDS-DMA staging: wave w moves rows 8 w .. 8 w + 7 of a tile (1 KB), lane l -> row 8 w + l / 8, physical chunk l % 8
     constexpr unsigned OOB = 0x80000000u;
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi32 = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi32) << 32));
-    };
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(kp), 0, __builtin_amdgcn_readfirstlane(((p.nk - 1) * p.k_ld + D) * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(
@@ -1096,12 +1084,6 @@ __global__ __launch_bounds__(512, 1) void k_attention_pp2(const AttnParams p) {
     const float c2 = p.scale_log2e;
     const int nkt = p.nk / KT, npair = nkt / 2;                                  // (launcher: nk % 128 == 0)
 
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi32 = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi32) << 32));
-    };
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(kp), 0, __builtin_amdgcn_readfirstlane(((p.nk - 1) * p.k_ld + D) * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(

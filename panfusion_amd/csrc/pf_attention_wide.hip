@@ -110,12 +110,6 @@ __global__ __launch_bounds__(256, 1) void k_attention_wide(const WideParams p) {
     // them at D = 512 pushed the kernel into scratch).  Every offset is kept inside the slice by construction (the last tile clamps its
     // rows / pieces); the descriptors also END with the slice -- K after key nk - 1, V^T after row D - 1.
     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi_ = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi_) << 32));
-    };
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(kp), 0, ((p.nk - 1) * p.k_ld + D) * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(vp), 0, D * p.vt_ld * 2, 0x00020000);
     const unsigned kvoff = static_cast<unsigned>(tr * p.k_ld + tc * 8) * 2u;              // bytes

@@ -110,6 +110,19 @@ template <typename T> __device__ __forceinline__ void split8(const float (&f)[8]
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 
+// A pointer rebuilt from readfirstlane'd words, for buffer descriptors: hipcc otherwise treats a selected or computed descriptor as
+// divergent and wraps every access through it in a waterfall loop (cdna_hip_programming.md T20).
+template <typename T> __device__ __forceinline__ T* uniform_ptr(const T* ptr) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
+    const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
+    const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
+    return reinterpret_cast<T*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32));
+}
+// LDS-DMA of 16 bytes per lane (buffer_load_dwordx4 ... lds): lane l's bytes land at lds_dst + 16 l (lds_dst wave-uniform).
+__device__ __forceinline__ void lds_dma16(const __amdgpu_buffer_rsrc_t& rsrc, unsigned short* lds_dst, unsigned voff, int soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
+}
+
 // Element access by storage tag (fp32 / bf16 / fp16) for the kernels that take any of the three.
 template <typename S> __device__ __forceinline__ float ld_any(const void* p, long i);
 struct AnyF32 {}; struct AnyBf16 {}; struct AnyF16 {};

@@ -23,6 +23,7 @@
 // models/pano/MVGenModel.py:86-144,174-198,224-294; models/modules/transformer.py:8-74).
 #include "pf_common.h"
 #include "pf_gemm_params.h"
+#include "pf_gemm_walk.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -166,8 +167,6 @@ __device__ __forceinline__ void gn_moments_phase(const GemmParams& p, long bz, c
 // staged through LDS so that it leaves as whole 16-byte row segments (a fragment store touches 16
 // different rows with 8 bytes each).  fp32 output, ragged N or an unaligned out_ld take the direct
 // per-fragment store.  smem16: the block's LDS (the operand ring is dead after the K loop).
-struct NoOp { __device__ void operator()() const {} };
-
 // Staged block epilogue, specialised at compile time for the operand mix of the layer (MODE):
 //   0 bias | 1 bias + per-image row vector (time embedding) | 2 bias + residual | 3 bias + GEGLU pairing.
 // Straight-line code: rows beyond M / quads beyond N are CLAMPED to the last valid one instead of being
@@ -541,6 +540,10 @@ __device__ __forceinline__ void splitk_finish(const GemmParams& p, long bz, int 
 // weight DMA of that block, stay in flight during the MFMAs of block it, and become the two 16-byte pieces hi | lo (affine_f / split8, pf_common.h) that the
 // DMA of the pair tensor would have put at lds_off(row, c4) and lds_off(row, c4 + 4) -- written behind the same full drain and in front of the same barrier
 // that ends the step.  Fragment reads, MFMA order, split-K and every epilogue are the pair form's: the result is bit-identical.
+// This kernel keeps its OWN copy of the operand walk (pf_gemm_walk.h serves k_conv_gemm8 and k_conv_gemm32): folded onto ConvWalk every 16-bit
+// instantiation went from 0 to 4-15 spilled SGPRs (TotalSGPRs 79-96 -> 104-106, VGPRs + 1-5, one occupancy 3 -> 2), whichever way the rows, the bounds
+// test, the tile remap, the inlining or the launch constants were spelled; with its own text the registers are the ones it always had.  A change to
+// the walk is made in pf_gemm_walk.h AND here.  (Its uniform_ptr / lds_dma lambdas are part of that text and kept on purpose.)
 template <typename T, int MREP, int NREP, bool STATS = false, bool S3 = false, int STAGES = 2, bool A32 = false>
 __global__ __launch_bounds__(256, STAGES > 2 ? 1 : 2) void k_conv_gemm(const GemmParams p) {
     constexpr int BM = 32 * MREP, BN = 32 * NREP;
@@ -871,7 +874,6 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     const unsigned short* a1 = p.a1 ? p.a1 + bz * p.a_bs : nullptr;
     const unsigned short* wg = p.w + bz * p.w_bs;
     int m0 = 0, n0 = 0;                              // origin of the tile being multiplied (set_tile)
-    const int pad_y = p.subpix ? 1 - (static_cast<int>(bz) >> 1) : p.pad, pad_x = p.subpix ? 1 - (static_cast<int>(bz) & 1) : p.pad;   // (sub-pixel phase: pf_gemm_params.h)
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -889,23 +891,12 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
                                                      // image (rows per image are even: pf_conv_gemm checks), so one scale / shift octet serves both
     unsigned x_off[2];                               // bytes, or OOB
     int x_sidx = 0;                                  // element of a_scale / a_shift at channel 0 of the octet
-    int a_img[APASS], a_y[APASS], a_x[APASS];
     // DMA addressing: buffer descriptors (SGPR) + a per-thread 32-bit byte offset (VGPR) + a per-stage
     // scalar byte offset (soffset), so that a piece costs no vector ALU work per K step -- the kernel is
     // bound by instruction issue, not by the matrix pipe (4 issue slots of a SIMD per 16-clock MFMA,
     // shared by two waves).  Zero padding / ragged tiles: an offset beyond num_records reads as zero.
-    constexpr unsigned OOB = 0x80000000u;                         // launcher guarantees tensors < 2 GiB
-    // descriptors are built from readfirstlane'd words: hipcc otherwise treats a selected descriptor as
-    // divergent and wraps every DMA in a waterfall loop (cdna_hip_programming.md T20)
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32));
-    };
+    // The walk that produces them: pf_gemm_walk.h.
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wg), 0, __builtin_amdgcn_readfirstlane(p.w_bytes), 0x00020000);
-    // (the activation descriptor is rebuilt from scalars at the start of every stage: carried across
-    // the loop as a variable it would live in VGPRs again)
     unsigned w_off[BFULL + 1];                                    // bytes
 #ifdef PF_GEMM_BDIRECT        /* experiment: weight fragments straight from L1 / L2 into registers, no weight tile in LDS.
                                * Correct (68 GEMM / conv tests) and 2x SLOWER (3x3 convs 850 -> 440 TF/s): a fragment-shaped load touches 16
@@ -914,107 +905,40 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     unsigned wb_off[NREP];                                        // bytes: (n of fragment j, this lane's k chunk)
     int kw = 0;                                                   // K offset (elements) of the stage being multiplied
 #endif
-    const int Ctot = p.c0 + p.c1;
-    const int Hl = p.h_in << p.up, Wl = (p.w_in + 2 * p.wrap) << p.up;
-
-    // K walk (wave-uniform): K-block = (tap, source, 64-channel block).  Per-thread activation offsets
-    // change only when the tap or the source changes ("segment"); inside a segment only soffset moves.
+    // K blocks [kb0, kb1) of this split-K slice
     const int nkb = p.K / 64;
     const int kb0 = blockIdx.y * p.kb_per_split;
     const int kb1 = min(nkb, kb0 + p.kb_per_split);
     const int n_it = kb1 - kb0;
-    int kg = 0, tap = 0, cc = 0;
-    unsigned a_off[APASS];                                        // bytes, or OOB
-    bool seg1 = false;                                            // current source is a1
-    auto set_segment = [&]() __attribute__((always_inline)) {
-        const int ky = p.ksize == 3 ? tap / 3 : p.ksize == 2 ? tap >> 1 : 0, kx = p.ksize == 3 ? tap - 3 * ky : p.ksize == 2 ? tap & 1 : 0;
-        seg1 = __builtin_amdgcn_readfirstlane(cc >= p.c0 ? 1 : 0) != 0;
-        const int ld = seg1 ? p.a1_ld : p.a0_ld;
-        if constexpr (A32) {                                           // 1x1: a row IS its pixel; rows past M read as zero (and become `shift` under the affine map: never stored, masked in the moments)
+    ConvWalk<APASS, 64, true, true, A32> w;                       // staged rows i * RPP + lrow of the tile
+    w.init(p, bz);
+    // A32, every new segment: 1x1, a row IS its pixel; rows past M read as zero (and become `shift` under the affine map: never stored, masked in the moments)
+    auto a32_rows = [&]() __attribute__((always_inline)) {
+        const int ld = w.seg1 ? p.a1_ld : p.a0_ld;
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int m = m0 + r32 + u;
-                x_off[u] = m < p.M ? (static_cast<unsigned>(m) * static_cast<unsigned>(ld) + 8u * c4) * 4u : OOB;
-            }
-            return;
-        }
-        if (p.fastseg) {                                               // (pf_gemm_params.h: a_img = pixel index, a_y = validity bits)
-            const unsigned sel = (1u << ky) | (16u << kx);
-            const int tap_pix = ky * p.w_in + kx;
-#pragma unroll
-            for (int i = 0; i < APASS; ++i) {
-                const unsigned off = ((static_cast<unsigned>(a_img[i]) + static_cast<unsigned>(tap_pix)) * static_cast<unsigned>(ld) + static_cast<unsigned>(lchunk8)) * 2u;
-                a_off[i] = (static_cast<unsigned>(a_y[i]) & sel) == sel ? off : OOB;
-            }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < APASS; ++i) {
-            const int yi = a_y[i] + ky, xi = a_x[i] + kx;             // xi: column in the (virtually wrap-padded, upsampled) input
-            const bool ok = yi >= 0 && yi < Hl && xi >= 0 && xi < Wl;
-            int sx = (xi >> p.up) - p.wrap;                            // source column: the padding is circular
-            sx += sx < 0 ? p.w_in : 0;
-            sx -= sx >= p.w_in ? p.w_in : 0;
-            const int pix = (a_img[i] * p.h_in + (yi >> p.up)) * p.w_in + sx;
-            a_off[i] = ok ? static_cast<unsigned>(pix * ld + lchunk8) * 2u : OOB;
+        for (int u = 0; u < 2; ++u) {
+            const int m = m0 + r32 + u;
+            x_off[u] = m < p.M ? (static_cast<unsigned>(m) * static_cast<unsigned>(ld) + 8u * c4) * 4u : GEMM_OOB;
         }
     };
-    // Persistent over tiles: a block walks tiles blockIdx.x, + gridDim.x, ...; all per-tile state is set here.
-    // (XCD-aware, bijective remap of the tile id: block b and all its tiles live on XCD b % 8.)
+    // Persistent over tiles: a block walks tiles blockIdx.x, + gridDim.x, ...; all per-tile state is set here (this runs once per tile on every thread).
     auto set_tile = [&](int tile) __attribute__((always_inline)) {
-        int tid_lin = tile;
-        {
-            const int q = ntile_total >> 3, r = ntile_total & 7;
-            const int xcd = tid_lin & 7, idx = tid_lin >> 3;
-            tid_lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        const int tid_lin = xcd_tile(tile, ntile_total);
         const int tile_m = static_cast<unsigned>(tid_lin) / static_cast<unsigned>(p.ntiles), tile_n = tid_lin - tile_m * p.ntiles;
         m0 = p.m_begin + tile_m * BM;
         n0 = tile_n * BN;
-        {
-            // output row -> (image, y, x): two divisions for the first DMA pass, then the host-computed
-            // advance of RPP rows with one carry per level (this runs once per tile on every thread)
-            const unsigned m = static_cast<unsigned>(m0 + lrow);
-            int img = static_cast<int>(m / static_cast<unsigned>(p.rows_per_img));
-            const unsigned rem = m - static_cast<unsigned>(img) * static_cast<unsigned>(p.rows_per_img);
-            int yo = static_cast<int>(rem / static_cast<unsigned>(p.w_out));
-            int xo = static_cast<int>(rem) - yo * p.w_out;
+        if constexpr (!A32) w.rows_by_advance(p, m0, lrow, RPP);
 #pragma unroll
-            for (int i = 0; i < APASS; ++i) {
-                const bool ok = m0 + i * RPP + lrow < p.M;
-                a_img[i] = ok ? img : 0;
-                a_y[i] = ok ? yo * p.stride - pad_y : -(1 << 20);
-                a_x[i] = (xo + p.crop) * p.stride - pad_x;
-                if (p.fastseg) seg_pack(a_img[i], a_y[i], a_x[i], p.h_in, p.w_in);
-                xo += p.adv_x;
-                if (xo >= p.w_out) { xo -= p.w_out; ++yo; }
-                yo += p.adv_y;
-                if (yo >= p.h_out) { yo -= p.h_out; ++img; }
-                img += p.adv_img;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BFULL; ++j) {
-            const int n = n0 + j * RPP + lrow;
-            w_off[j] = n < p.N ? static_cast<unsigned>(n * p.K + lchunk8) * 2u : OOB;
-        }
-        {
-            const int n = n0 + BFULL * RPP + hrow;
-            w_off[BFULL] = (BHALF && n < p.N) ? static_cast<unsigned>(n * p.K + hchunk8) * 2u : OOB;
-        }
-        kg = kb0 * 64;
-        tap = kg / Ctot;
-        cc = kg - tap * Ctot;
-        if constexpr (A32) {
-            if constexpr (AFF) x_sidx = (min(m0 + r32, p.M - 1) / p.rows_per_img) * (Ctot >> 1) + 8 * c4;
-        }
-        set_segment();
+        for (int j = 0; j < BFULL; ++j) w_off[j] = weight_row_offset(p, n0 + j * RPP + lrow, lchunk8);
+        w_off[BFULL] = BHALF ? weight_row_offset(p, n0 + BFULL * RPP + hrow, hchunk8) : GEMM_OOB;
+        if constexpr (A32 && AFF) x_sidx = (min(m0 + r32, p.M - 1) / p.rows_per_img) * (w.Ctot >> 1) + 8 * c4;
+        w.start(p, kb0 * 64, lchunk8, a32_rows);
 #ifdef PF_GEMM_BDIRECT
         kw = kb0 * 64;
 #pragma unroll
         for (int j = 0; j < NREP; ++j) {
             const int n = n0 + (wave & 1) * 16 * NREP + j * 16 + (lane & 15);
-            wb_off[j] = n < p.N ? static_cast<unsigned>(n * p.K + (lane >> 4) * 8) * 2u : OOB;
+            wb_off[j] = n < p.N ? static_cast<unsigned>(n * p.K + (lane >> 4) * 8) * 2u : GEMM_OOB;
         }
 #endif
     };
@@ -1024,21 +948,8 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
     // for ~900 clocks: the CU's vector-memory pipe moves ~64 B/clk).
     constexpr int NPIECE = APASS + BFULL + (BHALF ? 1 : 0);
     int st_soff_a = 0, st_soff_w = 0;
-    auto stage_begin = [&]() __attribute__((always_inline)) {
-        st_soff_a = __builtin_amdgcn_readfirstlane((seg1 ? cc - p.c0 : cc) * 2);
-        st_soff_w = __builtin_amdgcn_readfirstlane(kg * 2);
-        return __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(seg1 ? a1 : a0), 0,
-                                                 __builtin_amdgcn_readfirstlane(seg1 ? p.a1_bytes : p.a0_bytes), 0x00020000);
-    };
-    auto stage_end = [&]() __attribute__((always_inline)) {
-        kg += 64;
-        cc += 64;
-        if (cc == Ctot) { cc = 0; ++tap; set_segment(); }
-        else if (cc == p.c0) set_segment();
-    };
-    auto lds_dma = [&](const __amdgpu_buffer_rsrc_t& r, unsigned short* dst, unsigned voff, int soff) __attribute__((always_inline)) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-    };
+    auto stage_begin = [&]() __attribute__((always_inline)) { return w.stage_begin(p, a0, a1, st_soff_a, st_soff_w); };
+    auto stage_end = [&]() __attribute__((always_inline)) { w.stage_end(p, lchunk8, a32_rows); };
     auto dma_piece = [&](const __amdgpu_buffer_rsrc_t& rs_a, int slot, int k, XR& q) __attribute__((always_inline)) {
         unsigned short* As = smem + slot * STAGE;
         unsigned short* Bs = As + BM * 64;
@@ -1046,19 +957,19 @@ __global__ __launch_bounds__(64 * NW, BM_ == 128 ? 2 : 1) void k_conv_gemm8(cons
             if constexpr (A32) {                                  // half an fp32 octet into registers (a32_write puts it into the slot)
                 const int u = k >> 1, hf = k & 1;
                 q.x[u][hf] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, x_off[u] + 16u * hf, st_soff_a, 0));
-                if (k == 0) q.cc = cc;
+                if (k == 0) q.cc = w.cc;
                 return;
             }
             unsigned short* dst = As + (k * RPP + wave * 8) * 64;
-            lds_dma(rs_a, dst, a_off[k], st_soff_a);
+            lds_dma16(rs_a, dst, w.off[k], st_soff_a);
 #ifdef PF_GEMM_BDIRECT
         } else if (true) {
 #endif
         } else if (k < APASS + BFULL) {
             const int j = k - APASS;
-            lds_dma(rs_w, Bs + (j * RPP + wave * 8) * 64, w_off[j], st_soff_w);
+            lds_dma16(rs_w, Bs + (j * RPP + wave * 8) * 64, w_off[j], st_soff_w);
         } else if (BHALF) {
-            if (lane < 32) lds_dma(rs_w, Bs + (BFULL * RPP + wave * 4) * 64, w_off[BFULL], st_soff_w);
+            if (lane < 32) lds_dma16(rs_w, Bs + (BFULL * RPP + wave * 4) * 64, w_off[BFULL], st_soff_w);
         }
     };
     auto dma_stage = [&](int slot, XR& q) __attribute__((always_inline)) {

@@ -22,10 +22,11 @@
 //   * epilogue straight from the fragments: fp32 rows as 16-byte quads; 16-bit rows after a v_permlane32_swap that gives every lane
 //     8 consecutive channels (16 bytes).  No LDS staging: the ring is free for the next tile's first four stages at once.
 // Addressing (scalar buffer descriptors + per-thread byte offsets + per-stage scalar offsets, zero padding as out-of-range offsets,
-// stride 2, fused nearest x2 upsampling, channel concat of two sources, virtual circular padding), the XCD-aware tile order, split K
-// over blockIdx.y and the GroupNorm-moment by-product follow pf_gemm.hip.
+// stride 2, fused nearest x2 upsampling, channel concat of two sources, virtual circular padding) and the XCD-aware tile order are the
+// operand walk shared with pf_gemm.hip (pf_gemm_walk.h); split K over blockIdx.y and the GroupNorm-moment by-product follow pf_gemm.hip.
 #include "pf_common.h"
 #include "pf_gemm_params.h"
+#include "pf_gemm_walk.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -242,117 +243,45 @@ __global__ __launch_bounds__(512, 1) void k_conv_gemm32(const GemmParams p) {
     const int hchunk8 = ((lane & 3) ^ ((hrow >> 2) & 3)) * 8;
 #endif
 
-    int a_img[2], a_y[2], a_x[2];
-    constexpr unsigned OOB = 0x80000000u;                         // launcher guarantees tensors < 2 GiB
-    auto uniform_ptr = [](const unsigned short* ptr) __attribute__((always_inline)) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32));
-    };
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wg), 0, __builtin_amdgcn_readfirstlane(p.w_bytes), 0x00020000);
     unsigned w_off[3];
-    const int Ctot = p.c0 + p.c1;
-    const int Hl = p.h_in << p.up, Wl = (p.w_in + 2 * p.wrap) << p.up;
 
-    // K walk in 32-element blocks (wave-uniform): block = (tap, source, 32 channels).  kb_per_split counts 64-element blocks.
+    // The operand walk (pf_gemm_walk.h) in 32-element K blocks; kb_per_split counts 64-element blocks.  The general segment form only, no
+    // sub-pixel phases: launch_gemm32 refuses what this instantiation does not walk.
     const int nkb = p.K / BK;
     const int kb0 = blockIdx.y * p.kb_per_split * 2;
     const int kb1 = min(nkb, kb0 + p.kb_per_split * 2);
     const int n_it = kb1 - kb0;
-    int kg = 0, tap = 0, cc = 0;
-    unsigned a_off[2];
-    bool seg1 = false;
-    auto set_segment = [&]() __attribute__((always_inline)) {
-        const int ky = p.ksize == 3 ? tap / 3 : 0, kx = p.ksize == 3 ? tap - 3 * ky : 0;
-        seg1 = __builtin_amdgcn_readfirstlane(cc >= p.c0 ? 1 : 0) != 0;
-        const int ld = seg1 ? p.a1_ld : p.a0_ld;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int yi = a_y[i] + ky, xi = a_x[i] + kx;
-            // (no short-circuit: hipcc keeps && as nested exec-masked branches and sinks the uniform K-walk updates into them)
-            const bool ok = (static_cast<unsigned>(yi) < static_cast<unsigned>(Hl)) & (static_cast<unsigned>(xi) < static_cast<unsigned>(Wl));
-            int sx = (xi >> p.up) - p.wrap;
-            sx += sx < 0 ? p.w_in : 0;
-            sx -= sx >= p.w_in ? p.w_in : 0;
-            const int pix = (a_img[i] * p.h_in + (yi >> p.up)) * p.w_in + sx;
-            a_off[i] = ok ? static_cast<unsigned>(pix * ld + lchunk8) * 2u : OOB;
-        }
-    };
+    ConvWalk<2, BK, false, false> w;                              // staged rows i * 128 + lrow of the tile
+    w.init(p, bz);
     auto set_tile = [&](int tile) __attribute__((always_inline)) {
-        int tid_lin = tile;
-        {
-            const int q = ntile_total >> 3, r = ntile_total & 7;
-            const int xcd = tid_lin & 7, idx = tid_lin >> 3;
-            tid_lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        const int tid_lin = xcd_tile(tile, ntile_total);
         const int tile_m = static_cast<unsigned>(tid_lin) / static_cast<unsigned>(p.ntiles), tile_n = tid_lin - tile_m * p.ntiles;
         m0 = p.m_begin + tile_m * BM;
         n0 = tile_n * BN;
-        {
-            const unsigned m = static_cast<unsigned>(m0 + lrow);
-            int img = static_cast<int>(m / static_cast<unsigned>(p.rows_per_img));
-            const unsigned rem = m - static_cast<unsigned>(img) * static_cast<unsigned>(p.rows_per_img);
-            int yo = static_cast<int>(rem / static_cast<unsigned>(p.w_out));
-            int xo = static_cast<int>(rem) - yo * p.w_out;
+        w.rows_by_advance(p, m0, lrow, 128);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const bool ok = m0 + i * 128 + lrow < p.M;
-                a_img[i] = ok ? img : 0;
-                a_y[i] = ok ? yo * p.stride - p.pad : -(1 << 20);
-                a_x[i] = (xo + p.crop) * p.stride - p.pad;
-                xo += p.adv_x;
-                if (xo >= p.w_out) { xo -= p.w_out; ++yo; }
-                yo += p.adv_y;
-                if (yo >= p.h_out) { yo -= p.h_out; ++img; }
-                img += p.adv_img;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + j * 128 + lrow;
-            w_off[j] = n < p.N ? static_cast<unsigned>(n * p.K + lchunk8) * 2u : OOB;
-        }
-        {
-            const int n = n0 + 256 + hrow;
-            w_off[2] = n < p.N ? static_cast<unsigned>(n * p.K + hchunk8) * 2u : OOB;
-        }
-        // (integer division runs on the vector ALU: without the readfirstlane hipcc treats the whole K walk as divergent and puts
-        // every stage_end() under exec masks)
-        kg = kb0 * BK;
-        tap = __builtin_amdgcn_readfirstlane(kg / Ctot);
-        cc = __builtin_amdgcn_readfirstlane(kg - tap * Ctot);
-        set_segment();
+        for (int j = 0; j < 2; ++j) w_off[j] = weight_row_offset(p, n0 + j * 128 + lrow, lchunk8);
+        w_off[2] = weight_row_offset(p, n0 + 256 + hrow, hchunk8);
+        w.start(p, kb0 * BK, lchunk8);
     };
 
     int st_soff_a = 0, st_soff_w = 0;
     auto stage_begin = [&]() __attribute__((always_inline)) {
+        const __amdgpu_buffer_rsrc_t rs_a = w.stage_begin(p, a0, a1, st_soff_a, st_soff_w);
 #ifdef PF_ABL_FULLLINE
-        st_soff_a = __builtin_amdgcn_readfirstlane(((seg1 ? cc - p.c0 : cc) * 4) % ((seg1 ? p.c1 : p.c0) * 2));
-        st_soff_w = __builtin_amdgcn_readfirstlane((kg * 4) % (p.K * 2));
-#else
-        st_soff_a = __builtin_amdgcn_readfirstlane((seg1 ? cc - p.c0 : cc) * 2);
-        st_soff_w = __builtin_amdgcn_readfirstlane(kg * 2);
+        st_soff_a = __builtin_amdgcn_readfirstlane(((w.seg1 ? w.cc - p.c0 : w.cc) * 4) % ((w.seg1 ? p.c1 : p.c0) * 2));
+        st_soff_w = __builtin_amdgcn_readfirstlane((w.kg * 4) % (p.K * 2));
 #endif
-        return __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(seg1 ? a1 : a0), 0,
-                                                 __builtin_amdgcn_readfirstlane(seg1 ? p.a1_bytes : p.a0_bytes), 0x00020000);
+        return rs_a;
     };
-    auto stage_end = [&]() __attribute__((always_inline)) {
-        kg = __builtin_amdgcn_readfirstlane(kg + BK);
-        cc = __builtin_amdgcn_readfirstlane(cc + BK);
-        tap = __builtin_amdgcn_readfirstlane(tap);
-        if (cc == Ctot) { cc = 0; ++tap; set_segment(); }
-        else if (cc == p.c0) set_segment();
-    };
-    auto lds_dma = [&](const __amdgpu_buffer_rsrc_t& r, unsigned short* dst, unsigned voff, int soff) __attribute__((always_inline)) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-    };
+    auto stage_end = [&]() __attribute__((always_inline)) { w.stage_end(p, lchunk8); };
     auto dma_piece = [&](const __amdgpu_buffer_rsrc_t& rs_a, int slot, int k) __attribute__((always_inline)) {
         unsigned short* As = smem + slot * STAGE;
         unsigned short* Ws = As + BM * BK;
-        if (k < 2) lds_dma(rs_a, As + (k * 128 + wave * 16) * BK, a_off[k], st_soff_a);
-        else if (k < 4) lds_dma(rs_w, Ws + ((k - 2) * 128 + wave * 16) * BK, w_off[k - 2], st_soff_w);
-        else if (lane < 32) lds_dma(rs_w, Ws + (256 + wave * 8) * BK, w_off[2], st_soff_w);
+        if (k < 2) lds_dma16(rs_a, As + (k * 128 + wave * 16) * BK, w.off[k], st_soff_a);
+        else if (k < 4) lds_dma16(rs_w, Ws + ((k - 2) * 128 + wave * 16) * BK, w_off[k - 2], st_soff_w);
+        else if (lane < 32) lds_dma16(rs_w, Ws + (256 + wave * 8) * BK, w_off[2], st_soff_w);
     };
     auto dma_stage = [&](int slot) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rs_a = stage_begin();
@@ -634,6 +563,9 @@ static pf_status launch32_s(const GemmParams& gp, int batch, hipStream_t st) {
 
 // Launches the 32x32 kernel on [gp.m_begin, gp.M) (the split-K reduce, if any, is the caller's: pf_gemm.hip owns k_splitk_reduce).
 pf_status launch_gemm32(const GemmParams& gp, int dtype, int batch, hipStream_t st) {
+    // what the kernel's instantiation of the walk does not do (the planner sends it none of these)
+    PF_REQUIRE(!gp.subpix && (gp.ksize == 1 || gp.ksize == 3), "pf_conv_gemm (32x32): no sub-pixel phases, ksize 1 or 3 only (ksize %d)", gp.ksize);
+    PF_REQUIRE(!gp.s3, "pf_conv_gemm (32x32): no split-precision walk");
     PF_DISPATCH_16(dtype, "pf_conv_gemm", return gp.gn_partial ? launch32_s<T, true>(gp, batch, st) : launch32_s<T, false>(gp, batch, st));
     return PF_OK;
 }

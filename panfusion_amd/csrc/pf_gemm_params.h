@@ -1,5 +1,6 @@
 // Shared by the tile GEMM kernels (pf_gemm.hip: 16x16x32 MFMA tiles; pf_gemm32.hip: 32x32x16 MFMA tiles): kernel parameters, phase stamps,
-// the per-quad generic epilogue and the split-K slab store.
+// the per-quad generic epilogue and the split-K slab store.  The address arithmetic that these parameters drive -- K walk, staged rows, segment
+// offsets (seg_pack below is its packed row state), tile decode -- is ONE piece of device code for the 8-wave and the 32x32 kernel: pf_gemm_walk.h (the 4-wave kernel keeps a copy).
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -155,10 +156,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, long bz, int
 __device__ __forceinline__ void slab_store(const GemmParams& p, long elem, const f32x4& v) {
     if (p.tickets) {
         typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-        const unsigned long long a = reinterpret_cast<unsigned long long>(p.partial);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a)), hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(a >> 32));
-        float* base = reinterpret_cast<float*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32));
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xFFFFFFFFu, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(p.partial), 0, 0xFFFFFFFFu, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, static_cast<int>(static_cast<unsigned>(elem * 4)), 0, /* sc1 */ 16);
     } else {
         *reinterpret_cast<float4*>(p.partial + elem) = float4{v[0], v[1], v[2], v[3]};

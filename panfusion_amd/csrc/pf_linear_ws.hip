@@ -84,12 +84,6 @@ __device__ __forceinline__ void lws_wave(const LwsParams& p, unsigned short* sme
     const int chunk = lane & 7;
     auto piece_row = [&](int i) { return ((wave * LWS_PIECES + i) % RG) * 8 + (lane >> 3); };
     auto piece_kb = [&](int i) { return (wave * LWS_PIECES + i) / RG; };
-    auto uniform_ptr = [](const unsigned short* ptr) {
-        const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
-        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
-        const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
-        return reinterpret_cast<unsigned short*>(static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32));
-    };
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(p.a), 0, __builtin_amdgcn_readfirstlane(p.a_bytes), 0x00020000);
     auto dma_tile = [&](int tile, int slot) {                     // rows past M: an offset beyond num_records reads as zero
         unsigned short* dst = smem + slot * LWS_STAGE_ELEMS;
@@ -100,8 +94,7 @@ __device__ __forceinline__ void lws_wave(const LwsParams& p, unsigned short* sme
             const unsigned src_lane = static_cast<unsigned>(lrow * p.a_ld + ((chunk ^ ((lrow >> 1) & 7)) << 3)) * 2u;   // bytes
             const unsigned voff = tile * LWS_BM + lrow < p.M ? src_lane : 0x80000000u;
             const int rg8 = __builtin_amdgcn_readfirstlane(((wave * LWS_PIECES + i) % RG) * 8);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (__attribute__((address_space(3))) void*)(dst + kb * LWS_BM * 64 + rg8 * 64), 16,
-                                                     voff, soff0 + kb * 128, 0, 0);
+            lds_dma16(rs_a, dst + kb * LWS_BM * 64 + rg8 * 64, voff, soff0 + kb * 128);
         }
         __builtin_amdgcn_sched_barrier(0);                        // (program order of the vector-memory operations is what the counted wait counts)
     };

@@ -1420,19 +1420,42 @@ def test_conv_gemm32_groupnorm_moments(dtype, f32out, gemm32_on):
 # ------------------------------------------------------------------------------------ sub-pixel upsampling convolution
 
 
-@pytest.mark.parametrize("case", ["conv3_8wave", "conv3_4wave", "conv3_ragged", "concat", "stride2_pad_hi", "subpixel", "splitk", "split3_1x1"])
-def test_conv_gemm_packed_tap_offsets_same_bits(case, monkeypatch):
+# Split-K slices that start INSIDE the operand walk (ConvWalk::start, pf_gemm_walk.h): at a tap > 0, exactly at the switch to the second source
+# (cc == c0) or inside it.  3x3, pad 1, bias, two sources of different widths (the other split-K tests use c0 == c1 and whole-tap slices).
+# id: (PF_GEMM32, (n, h, w), wrap_pad, (c0, c1), n_out, plan = (kernel, ring_slots or None, block_rows or None, m_split, slices, K blocks per slice),
+#      slice starts (tap, cc) -- what pf_conv_gemm_plan gives, host arithmetic)
+SPLIT_START_CASES = {
+    "4wave_deep_ring": (False, (1, 8, 16), 0, (64, 128), 64, (0, 4, None, 0, 6, 5), [(0, 0), (1, 128), (3, 64), (5, 0), (6, 128), (8, 64)]),
+    "4wave_two_slot": (False, (8, 32, 76), 2, (64, 128), 64, (0, 2, None, 0, 2, 14), [(0, 0), (4, 128)]),
+    "8wave_split": (False, (1, 64, 128), 0, (128, 128), 64, (1, None, 256, 0, 2, 18), [(0, 0), (4, 128)]),
+    "8wave_tail": (False, (8, 64, 128), 2, (192, 128), 64, (1, None, None, 65536, 5, 9), [(0, 0), (1, 256), (3, 192), (5, 128), (7, 64)]),
+    "k32_tail": (True, (20, 64, 64), 0, (128, 192), 320, (2, None, None, 65536, 4, 12), [(0, 0), (2, 128), (4, 256), (7, 64)]),
+}
+
+
+@pytest.mark.parametrize("case", ["conv3_8wave", "conv3_4wave", "conv3_ragged", "concat", "stride2_pad_hi", "subpixel", "splitk", "split3_1x1",
+                                  "4wave_deep_ring", "8wave_split", "k32_tail"])
+def test_conv_gemm_packed_tap_offsets_same_bits(case, monkeypatch, request):
     """GemmParams.fastseg: layers without upsampling / circular wrap keep a linear pixel index + one validity bit per tap row /
     column per staged tile row, and a tap change is an add, a multiply-add and a select.  Same addresses -> the results must be bit-identical to
     the general per-tap computation (PF_CONV_FASTSEG=0, read per call): 8-wave and 4-wave plans, a ragged last tile, a channel concat (two sources,
-    two leading dimensions), stride 2 with the VAE's bottom / right zero row, the sub-pixel upsampling form, a split-K plan, a split-precision 1x1."""
+    two leading dimensions), stride 2 with the VAE's bottom / right zero row, the sub-pixel upsampling form, a split-K plan, a split-precision 1x1,
+    and the SPLIT_START_CASES without circular wrap (split-K slices that start inside the walk; k32_tail: the 32x32x16 kernel has the general form
+    only and must not change with the knob)."""
     from panfusion_amd import engine
     o = ops()
     g = torch.Generator(device=DEV).manual_seed(11)
-    n, h, w, c0, c1, cout, ks, stride, pad, pad_hi = {
+    if case == "k32_tail":
+        request.getfixturevalue("gemm32_on")
+    shapes = {
         "conv3_8wave": (8, 32, 32, 320, 0, 320, 3, 1, 1, 0), "conv3_4wave": (2, 12, 20, 128, 0, 192, 3, 1, 1, 0), "conv3_ragged": (3, 13, 17, 192, 0, 320, 3, 1, 1, 0),
         "concat": (4, 16, 16, 320, 192, 320, 3, 1, 1, 0), "stride2_pad_hi": (2, 32, 32, 128, 0, 128, 3, 2, 0, 1), "subpixel": (3, 10, 12, 128, 0, 192, 3, 1, 1, 0),
-        "splitk": (2, 8, 8, 1280, 0, 1280, 3, 1, 1, 0), "split3_1x1": (1, 1, 4096, 320, 0, 320, 1, 1, 0, 0)}[case]
+        "splitk": (2, 8, 8, 1280, 0, 1280, 3, 1, 1, 0), "split3_1x1": (1, 1, 4096, 320, 0, 320, 1, 1, 0, 0)}
+    if case in SPLIT_START_CASES:
+        _, (n, h, w), _, (c0, c1), cout, _, _ = SPLIT_START_CASES[case]
+        ks, stride, pad, pad_hi = 3, 1, 1, 0
+    else:
+        n, h, w, c0, c1, cout, ks, stride, pad, pad_hi = shapes[case]
     x0 = torch.randn(n, h, w, c0, device=DEV, generator=g).half()
     x1 = torch.randn(n, h, w, c1, device=DEV, generator=g).half() if c1 else None
     bias = torch.randn(cout, device=DEV, generator=g)
@@ -1450,12 +1473,56 @@ def test_conv_gemm_packed_tap_offsets_same_bits(case, monkeypatch):
         wt = (torch.randn(cout, ks * ks * (c0 + c1), device=DEV, generator=g) / (ks * ks * (c0 + c1)) ** 0.5).half()
         if pad_hi:
             kw.update(pad_hi=1)
+    if case == "k32_tail":
+        assert o.conv_gemm(x0, wt, cout, a1=x1, plan_only=True, **kw) == 2, "this shape is expected to take the 32x32x16 kernel"
     outs = []
     for env in ("0", "1"):
         monkeypatch.setenv("PF_CONV_FASTSEG", env)
         outs.append(o.conv_gemm(x0, wt, cout, a1=x1, **kw).clone())
     assert torch.isfinite(outs[0].float()).all() and outs[0].float().abs().max() > 0
     assert torch.equal(outs[0], outs[1]), "packed tap offsets changed the result (%s): max |d| %.3e" % (case, (outs[0].float() - outs[1].float()).abs().max().item())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", list(SPLIT_START_CASES))
+def test_conv_gemm_split_starts_inside_the_operand_walk(dtype, case, monkeypatch, request):
+    """ConvWalk::start (pf_gemm_walk.h), the one place where a K walk begins anywhere but at (tap 0, channel 0): every tile kernel on split-K
+    slices that start at a later tap, exactly at the switch to the second source and inside it, the sources having different widths.  The plan
+    is asserted first -- kernel, ring slots, slice starts -- so that a changed planner shows as a failed precondition, not as a test that walks
+    another path; then the launch against torch's fp32 convolution of the same 16-bit operands (circular pad for wrap_pad).  The cases with
+    wrap_pad take the general segment form, the others the packed one."""
+    o = ops()
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    g32, (n, h, w), wrap, (c0, c1), cout, (kernel, slots, block_rows, m_split, nsl, kb), starts = SPLIT_START_CASES[case]
+    if g32:
+        request.getfixturevalue("gemm32_on")
+    else:
+        o._PLANS.plans.clear()
+        monkeypatch.setenv("PF_GEMM32", "0")
+    g = torch.Generator(device=DEV).manual_seed(23)
+    x0 = torch.randn(n, h, w, c0, device=DEV, generator=g).to(dtype)
+    x1 = torch.randn(n, h, w, c1, device=DEV, generator=g).to(dtype)
+    wq = (torch.randn(cout, 9 * (c0 + c1), device=DEV, generator=g) / (9 * (c0 + c1)) ** 0.5).to(dtype)
+    b = torch.randn(cout, device=DEV, generator=g)
+    kw = dict(a1=x1, n_img=n, h_in=h, w_in=w, ksize=3, pad=1, bias=b, wrap_pad=wrap)
+    try:
+        plan = o.conv_gemm(x0, wq, cout, want_plan=True, **kw)
+        assert plan.kernel == kernel and plan.m_split == m_split, (plan.kernel, plan.m_split)
+        assert slots is None or plan.ring_slots == slots, plan.ring_slots
+        assert block_rows is None or plan.block_rows == block_rows, plan.block_rows
+        got_nsl, got_kb = (plan.tail_splits, plan.tail_kb) if m_split else (plan.splits, plan.kb_per_split)
+        assert (got_nsl, got_kb) == (nsl, kb), (got_nsl, got_kb)
+        assert [divmod(s * got_kb * 64, c0 + c1) for s in range(got_nsl)] == starts
+        got = o.conv_gemm(x0, wq, cout, **kw)
+    finally:
+        o._PLANS.plans.clear()
+    want = _conv_ref_gpu([x0, x1], wq, cout, 3, b, wrap=wrap)
+    assert got.shape == want.shape
+    # the reference differs from the kernel only by fp32 summation order; the operands are identical
+    check("split starts " + case, got, want, TOL[dtype])
+    check("split starts " + case + " (last rows)", got[-300:], want[-300:], TOL[dtype])
+    check("split starts " + case + " (first tile)", got[:256], want[:256], TOL[dtype])
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
